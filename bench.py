@@ -21,6 +21,14 @@ turn lengths) therefore vary per order; the distribution is reported.
 
 Reference implied operating point: ~0.011 decisions/sec (1 order / 90-120 s,
 BASELINE.md).
+
+A plain run sets up, warms up, times --steps steps and prints one JSON
+line (ms_per_step = wall milliseconds per timed step).  --dump-outputs DIR
+additionally writes the last timed step's per-decision results as
+DIR/<name>.npy (same arguments -> same order stream and prompts, so two
+builds can be compared decision for decision).  --full is reserved for
+secondary measurements; none exist yet, every reported field is a
+by-product of the timed steps.
 """
 
 from __future__ import annotations
@@ -55,7 +63,51 @@ def parse_args():
                         "scheduler")
     p.add_argument("--stub-llm", action="store_true",
                    help="CPU contract check: stub LLM instead of the GPU engine")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write the last timed step's "
+                        "per-decision results (what a caller of the agent "
+                        "pipeline receives) as DIR/<name>.npy")
+    p.add_argument("--full", action="store_true",
+                   help="also run the secondary measurements and checks; "
+                        "a plain run does only what the headline figure "
+                        "needs (today there are none: everything reported "
+                        "is a by-product of the timed steps)")
     return p.parse_args()
+
+
+# --dump-outputs: one row per decision of the last timed step, in order
+# of submission (the order of the step's slice of the order stream)
+DUMP_RESPONSE_BYTES = 1024   # response text cap per decision (-1 padded)
+
+
+def dump_outputs(path: str, results) -> None:
+    """Write what the timed path returned for its last step: the
+    (status, response) pair AI_RUN_AGENT yields per order plus the
+    episode counters, as float32 arrays."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = len(results)
+    resp = np.full((n, DUMP_RESPONSE_BYTES), -1.0, dtype=np.float32)
+    resp_len = np.zeros(n, dtype=np.float32)
+    for i, r in enumerate(results):
+        raw = (r.response or "").encode("utf-8")
+        resp_len[i] = len(raw)
+        raw = raw[:DUMP_RESPONSE_BYTES]
+        resp[i, :len(raw)] = np.frombuffer(raw, dtype=np.uint8)
+    arrays = {
+        "status": np.array([r.status == "SUCCESS" for r in results],
+                           dtype=np.float32),
+        "iterations": np.array([r.iterations for r in results],
+                               dtype=np.float32),
+        "tool_calls": np.array([r.tool_calls for r in results],
+                               dtype=np.float32),
+        "failures": np.array([r.failures for r in results],
+                             dtype=np.float32),
+        "response_len": resp_len,
+        "response_bytes": resp,
+    }
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, f"{name}.npy"), arr)
 
 
 def main():
@@ -191,6 +243,10 @@ def main():
             t = t.to(device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs,
+                     all_results[-args.batch:] if args.steps else [])
 
     total_decisions = args.batch * args.steps * world
     value = total_decisions / elapsed

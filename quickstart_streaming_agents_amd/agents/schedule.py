@@ -94,7 +94,8 @@ def run_episodes_continuous(episodes: list[Generator], llm,
                             tool: Callable[[str, dict], str],
                             max_tool_workers: int = 16,
                             decode_chunk: int = 8,
-                            tracer=None) -> list[EpisodeResult]:
+                            tracer=None,
+                            tool_lag: int = 1) -> list[EpisodeResult]:
     """Event-driven episode scheduler over the continuous-batching engine.
 
     `run_episodes` advances episodes in lockstep ROUNDS: every episode's
@@ -110,12 +111,22 @@ def run_episodes_continuous(episodes: list[Generator], llm,
     Requires the conversation-aware EngineLLM (submit_turn/pop_finished).
     tracer: optional runtime.trace.Tracer — one span per episode
     (submit -> finish wall time, iterations/tool calls in meta).
+
+    The schedule is a function of the inputs, not of tool round-trip
+    timing: a tool result re-enters its episode at a fixed slice — the
+    one `tool_lag` engine slices after the slice that issued the call
+    (so the round trip overlaps `tool_lag` slices of GPU work), or as
+    soon as the engine runs dry — in submission order, waiting for the
+    future if it has not landed yet.  The same inputs therefore form the
+    same prefill/decode batches, draw the same decision samples and
+    return the same results on every run.
     """
     import time as _time
     results: dict[int, EpisodeResult] = {}
     started: dict[int, float] = {}
-    tool_futs: dict[int, object] = {}
+    tool_futs: dict[int, tuple] = {}      # idx -> (future, issuing slice)
     n = len(episodes)
+    slice_no = 0
 
     def _advance(idx: int, send_value: Any, pool) -> None:
         try:
@@ -139,7 +150,8 @@ def run_episodes_continuous(episodes: list[Generator], llm,
             grammar = req[3] if len(req) > 3 else None
             llm.submit_turn(idx, req[1], req[2], grammar)
         elif req[0] == "tool":
-            tool_futs[idx] = pool.submit(_safe_tool, tool, req[1], req[2])
+            tool_futs[idx] = (pool.submit(_safe_tool, tool, req[1], req[2]),
+                              slice_no)
         else:
             raise ValueError(f"unknown request {req[0]!r}")
 
@@ -149,17 +161,19 @@ def run_episodes_continuous(episodes: list[Generator], llm,
             started[idx] = _time.perf_counter()
             _advance(idx, None, pool)
         while len(results) < n:
-            # tool completions first: their turns join this slice's admit
-            done_futs = [i for i, f in tool_futs.items() if f.done()]
-            for i in done_futs:
-                f = tool_futs.pop(i)
+            slice_no += 1
+            # tool results first: their turns join this slice's admit.
+            # Due = issued more than tool_lag slices ago, or everything
+            # outstanding when the engine has nothing to run.
+            idle = not (eng.pending or eng.running)
+            due = [i for i, (_, issued) in tool_futs.items()
+                   if idle or slice_no - issued > tool_lag]
+            for i in due:
+                f, _ = tool_futs.pop(i)
                 _advance(i, f.result(), pool)
             if eng.pending or eng.running:
                 eng.run_chunk(decode_chunk)
                 for cid, text in llm.pop_finished():
                     _advance(cid, text, pool)
-            elif tool_futs:
-                # nothing on the GPU: block briefly on tool I/O
-                _time.sleep(0.0005)
     llm.release_all()
     return [results[i] for i in range(n)]

@@ -135,7 +135,11 @@ class Engine:
         # on a given stack the engine falls back to eager decode.
         # TP NOTE: grammar decision sampling draws torch.rand — TP ranks
         # must share a seed so sampled decisions agree across the group.
-        self.use_graph = torch.cuda.is_available()
+        # Only a model that lives on the GPU is captured: capturing a CPU
+        # model on a GPU host records an empty graph whose replays emit
+        # nothing (every decoded token reads back as 0).
+        self.use_graph = torch.cuda.is_available() and \
+            torch.device(model.device).type == "cuda"
         self._graph = None
         self._graph_failed = False
         self._gbuf: dict = {}

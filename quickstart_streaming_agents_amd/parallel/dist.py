@@ -61,7 +61,7 @@ def init_distributed(tp_size: int = 1, backend: str | None = None,
         backend = "nccl" if use_cuda else "gloo"
     if not dist.is_initialized():
         dist.init_process_group(backend=backend)
-    if use_cuda:
+    if use_cuda and str(device).startswith("cuda"):
         torch.cuda.set_device(device)
     assert world % tp_size == 0, "world_size must divide by tp_size"
     tp_group = dp_group = None

@@ -100,7 +100,13 @@ def _shard_index_worker(rank, world, docs, queries):
 def _dp_metric_worker(rank, world):
     from quickstart_streaming_agents_amd.parallel.dist import (
         DistContext, init_distributed, max_over_ranks, sum_over_ranks)
-    ctx = init_distributed()
+    if torch.cuda.is_available() and torch.cuda.device_count() < world:
+        # fewer GPUs than ranks (e.g. a 1-GPU host): one rank per GPU is
+        # impossible, so run the same context + reductions over gloo/CPU
+        # as on a host without GPUs
+        ctx = init_distributed(backend="gloo", device="cpu")
+    else:
+        ctx = init_distributed()
     assert ctx.world_size == world and ctx.rank == rank
     s = sum_over_ranks(ctx, float(rank + 1))
     m = max_over_ranks(ctx, float(rank + 1))
