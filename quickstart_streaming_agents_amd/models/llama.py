@@ -33,6 +33,7 @@ the TP path run under multi-process gloo tests.
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 
 import torch
@@ -40,6 +41,13 @@ import torch.nn.functional as F
 
 from ..ops import dispatch as D
 from .kv_cache import PagedKVCache
+
+# QSA_PREFILL_V1=1 (read once, here) restores the three-kernel prefill path
+# (rope_inplace + kv_scatter + one-wave-per-q-block attention) for A/B runs;
+# tests flip the module attribute.
+PREFILL_V1 = os.environ.get("QSA_PREFILL_V1") == "1"
+# q rows per workgroup of the tiled prefill attention kernel
+PREFILL_TILE_ROWS = 32
 
 
 @dataclass
@@ -386,9 +394,12 @@ class LlamaModel:
         if use_hip_prefill:
             # varlen flash prefill over the paged cache: per-q-block maps
             # (one WAVE per 16 q rows x head in the kernel)
+            # (tiled kernel: one WORKGROUP per PREFILL_TILE_ROWS q rows x
+            # 4 heads; QSA_PREFILL_V1: one WAVE per 16 q rows x head)
+            qb_rows = 16 if PREFILL_V1 else PREFILL_TILE_ROWS
             qb_item, qb_pos0 = [], []
             for i, n in enumerate(lens):
-                for p0 in range(0, n, 16):
+                for p0 in range(0, n, qb_rows):
                     qb_item.append(i)
                     qb_pos0.append(p0)
             qb_item_t = torch.tensor(qb_item, dtype=torch.int32, device=dev)
@@ -433,15 +444,26 @@ class LlamaModel:
                                        c.norm_eps)
             qkv = F.linear(h, L["wqkv"], L.get("bqkv"))
             q, k, v = self._split_qkv(qkv, T_pad)
-            D.rope_inplace(q, k, self.rope_cos, self.rope_sin, positions)
-            D.kv_scatter(k[:T], v[:T], kv.k[li], kv.v[li], slots)
-            if use_hip_prefill:
-                # ONE varlen flash kernel: streams K/V pages directly, no
-                # gather/pad/score materialization
+            if use_hip_prefill and not PREFILL_V1:
+                # fused rope + cache scatter, then ONE varlen flash kernel
+                # that shares each K/V page through LDS: no gather/pad/
+                # score materialization
+                D.rope_kv_scatter(q, k, v, kv.k[li], kv.v[li], self.rope_cos,
+                                  self.rope_sin, positions, slots)
+                attn = D.ext().paged_attn_prefill_tiled(
+                    q, kv.k[li], kv.v[li], bt_t, qb_item_t, qb_pos0_t,
+                    off_t, start_t, len_t, self.scale, True,
+                    PREFILL_TILE_ROWS)
+            elif use_hip_prefill:
+                # the three-kernel path the fused one replaced (A/B runs)
+                D.rope_inplace(q, k, self.rope_cos, self.rope_sin, positions)
+                D.kv_scatter(k[:T], v[:T], kv.k[li], kv.v[li], slots)
                 attn = D.ext().paged_attn_prefill(
                     q, kv.k[li], kv.v[li], bt_t, qb_item_t, qb_pos0_t,
                     off_t, start_t, len_t, self.scale, True)
             else:
+                D.rope_inplace(q, k, self.rope_cos, self.rope_sin, positions)
+                D.kv_scatter(k[:T], v[:T], kv.k[li], kv.v[li], slots)
                 # padded q: [nb*nmax, n_q, D] -> [nb*KVH, R*nmax, D]
                 q_pad = torch.zeros(nb * nmax, self.n_q, c.d_head,
                                     dtype=self.dtype, device=dev)

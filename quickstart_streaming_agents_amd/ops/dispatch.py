@@ -148,6 +148,24 @@ def kv_scatter(knew: torch.Tensor, vnew: torch.Tensor, kc: torch.Tensor,
         vc[page, :, :, off] = vnew[t]
 
 
+def rope_kv_scatter(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                    kc: torch.Tensor, vc: torch.Tensor, cos_t: torch.Tensor,
+                    sin_t: torch.Tensor, positions: torch.Tensor,
+                    slots: torch.Tensor) -> None:
+    """Fused prefill rope + cache scatter.  q is rotated in place over all
+    its rows; the first T = slots.numel() rows of k (rotated) and v land in
+    the paged cache.  The fused kernel leaves k itself untouched (nothing
+    reads it afterwards); the CPU reference composes the two reference ops
+    and so also rotates k in place."""
+    if _cuda(q):
+        ext().rope_kv_scatter(q, k, v, kc, vc, cos_t, sin_t, positions,
+                              slots)
+        return
+    T = slots.numel()
+    rope_inplace(q, k, cos_t, sin_t, positions)
+    kv_scatter(k[:T], v[:T], kc, vc, slots)
+
+
 def paged_attn_decode(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
                       block_table: torch.Tensor, seq_lens: torch.Tensor,
                       scale: float) -> torch.Tensor:

@@ -52,6 +52,15 @@ extern "C" void qsa_paged_attn_prefill_launch(
     const int*, const int*, const int*, const int*, const int*, const int*,
     unsigned short*, float, int, int, int, int, int, long long, int,
     hipStream_t);
+extern "C" int qsa_paged_attn_prefill_tiled_launch(
+    const unsigned short*, const unsigned short*, const unsigned short*,
+    const int*, const int*, const int*, const int*, const int*, const int*,
+    unsigned short*, float, int, int, int, int, int, long long, int, int,
+    hipStream_t);
+extern "C" void qsa_rope_kv_scatter_launch(
+    unsigned short*, const unsigned short*, const unsigned short*,
+    unsigned short*, unsigned short*, const float*, const float*, const int*,
+    const int*, int, int, int, int, int, long long, long long, hipStream_t);
 extern "C" void qsa_rope_kv_append_launch(unsigned short*,
                                           const unsigned short*,
                                           const unsigned short*,
@@ -274,6 +283,95 @@ torch::Tensor paged_attn_prefill(torch::Tensor q, torch::Tensor kc,
       item_len.data_ptr<int>(), u16m(out), (float)scale, QB, QH, KVH, npmax,
       D, q.stride(0), causal ? 1 : 0, cur_stream());
   return out;
+}
+
+// Tiled prefill attention: tile maps at `rows` (32/64) q-row granularity.
+// Shapes the tiled kernel does not cover (GQA ratio not a multiple of 4)
+// run the one-wave-per-block kernel on 16-row maps expanded from the tiles;
+// a 16-row block that starts past its item's end masks every column and
+// stores nothing.
+torch::Tensor paged_attn_prefill_tiled(
+    torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
+    torch::Tensor block_table, torch::Tensor tile_item,
+    torch::Tensor tile_pos0, torch::Tensor item_off, torch::Tensor item_start,
+    torch::Tensor item_len, double scale, bool causal, long rows) {
+  CHK_DEV(q); CHK_BF16(q); CHK_BF16(kc); CHK_BF16(vc);
+  CHK_CONT(kc); CHK_CONT(vc); CHK_I32(block_table); CHK_CONT(block_table);
+  CHK_I32(tile_item); CHK_I32(tile_pos0); CHK_I32(item_off);
+  CHK_I32(item_start); CHK_I32(item_len);
+  CHK_CONT(tile_item); CHK_CONT(tile_pos0);
+  const int T = q.size(0), QH = q.size(1), D = q.size(2);
+  chk_hd_strided(q, D, "q");
+  const int KVH = kc.size(1);
+  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
+  TORCH_CHECK(rows == 32 || (rows == 64 && D == 64),
+              "rows must be 32 (or 64 at D == 64)");
+  TORCH_CHECK(QH % KVH == 0 && QH / KVH <= 16, "GQA ratio <= 16");
+  TORCH_CHECK(q.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
+              "q rows must be 16-byte aligned");
+  TORCH_CHECK(kc.size(2) == D / 8 && kc.size(3) == 64 && kc.size(4) == 8,
+              "K cache layout [P, KVH, D/8, 64, 8]");
+  TORCH_CHECK(vc.size(2) == D && vc.size(3) == 64, "V layout [P,KVH,D,64]");
+  TORCH_CHECK(tile_item.numel() == tile_pos0.numel(), "tile maps");
+  const int NT = tile_item.numel();
+  const int npmax = block_table.size(1);
+  auto out = torch::empty({(long long)T, (long long)QH * D}, q.options());
+  const int done = qsa_paged_attn_prefill_tiled_launch(
+      u16(q), u16(kc), u16(vc), block_table.data_ptr<int>(),
+      tile_item.data_ptr<int>(), tile_pos0.data_ptr<int>(),
+      item_off.data_ptr<int>(), item_start.data_ptr<int>(),
+      item_len.data_ptr<int>(), u16m(out), (float)scale, NT, QH, KVH, npmax,
+      D, q.stride(0), causal ? 1 : 0, (int)rows, cur_stream());
+  if (done) return out;
+  const long sub = rows / 16;
+  auto qb_item = tile_item.repeat_interleave(sub).contiguous();
+  auto step = torch::arange(sub, tile_pos0.options()) * 16;
+  auto qb_pos0 = (tile_pos0.unsqueeze(1) + step.unsqueeze(0))
+                     .reshape({-1}).contiguous();
+  return paged_attn_prefill(q, kc, vc, block_table, qb_item, qb_pos0,
+                            item_off, item_start, item_len, scale, causal);
+}
+
+// Fused prefill rope + KV scatter: q [Tq, QH, D] rotated in place over all
+// rows; the first T = slots.numel() rows of k (rotated) and v go straight
+// into the paged cache.  k itself is left untouched.
+void rope_kv_scatter(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                     torch::Tensor kc, torch::Tensor vc, torch::Tensor cos_t,
+                     torch::Tensor sin_t, torch::Tensor pos,
+                     torch::Tensor slots) {
+  CHK_DEV(q); CHK_BF16(q); CHK_BF16(k); CHK_BF16(v); CHK_BF16(kc);
+  CHK_BF16(vc); CHK_CONT(kc); CHK_CONT(vc);
+  CHK_F32(cos_t); CHK_F32(sin_t); CHK_CONT(cos_t); CHK_CONT(sin_t);
+  CHK_I32(pos); CHK_I32(slots); CHK_CONT(pos); CHK_CONT(slots);
+  const int Tq = q.size(0), QH = q.size(1), D = q.size(2);
+  const int KVH = k.size(1);
+  const int T = slots.numel();
+  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
+  chk_hd_strided(q, D, "q"); chk_hd_strided(k, D, "k");
+  chk_hd_strided(v, D, "v");
+  TORCH_CHECK(k.size(2) == D && v.size(2) == D && v.size(1) == KVH,
+              "k/v shape");
+  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v strides must match");
+  TORCH_CHECK(pos.numel() == Tq, "one position per q row");
+  TORCH_CHECK(T <= Tq && T <= k.size(0) && T <= v.size(0),
+              "slots longer than q/k/v");
+  TORCH_CHECK(kc.size(1) == KVH && kc.size(2) == D / 8 && kc.size(3) == 64 &&
+              kc.size(4) == 8, "K cache layout [P, KVH, D/8, 64, 8]");
+  TORCH_CHECK(vc.size(1) == KVH && vc.size(2) == D && vc.size(3) == 64,
+              "V cache layout [P, KVH, D, 64]");
+  auto al16 = [](const torch::Tensor& t) {
+    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+  };
+  TORCH_CHECK(q.stride(0) % 8 == 0 && k.stride(0) % 8 == 0 && al16(q) &&
+              al16(k) && al16(v) && al16(kc) && al16(cos_t) && al16(sin_t),
+              "rope_kv_scatter needs 16-byte aligned rows");
+  if (Tq == 0) return;
+  qsa_rope_kv_scatter_launch(u16m(q), u16(k), u16(v), u16m(kc), u16m(vc),
+                             cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
+                             pos.data_ptr<int>(), slots.data_ptr<int>(), Tq, T,
+                             QH, KVH, D, q.stride(0), k.stride(0),
+                             cur_stream());
 }
 
 void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -524,6 +622,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_attn_decode", &paged_attn_decode,
         "paged-attention decode (bf16, GQA, page=64)");
   m.def("kv_append", &kv_append, "append one step's k/v to the paged cache");
+  m.def("paged_attn_prefill_tiled", &paged_attn_prefill_tiled,
+        "varlen flash prefill attention, K/V pages shared through LDS");
+  m.def("rope_kv_scatter", &rope_kv_scatter,
+        "fused prefill rope + paged-cache scatter");
   m.def("rope_kv_append", &rope_kv_append,
         "fused decode rope + paged-cache append");
   m.def("kv_scatter", &kv_scatter, "scatter prefill k/v by slot ids");

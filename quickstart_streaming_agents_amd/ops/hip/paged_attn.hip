@@ -23,12 +23,21 @@
 //
 // The online softmax runs per head-column in registers: column max/sum
 // reduce with two shfl_xor hops (the 4 hi-lane groups of a column).
+//
+// Also in this file: the KV-cache writers (decode append, prefill scatter,
+// and the fused prefill rope + scatter qsa_rope_kv_scatter) and the two
+// varlen PREFILL attention kernels: qsa_paged_attn_prefill (one wave per
+// 16 q rows x head, fragments from global memory; the bit-exactness oracle
+// and the path for shapes the tiled kernel does not cover) and
+// qsa_paged_attn_prefill_tiled (one workgroup per 32/64 q rows x 4 heads,
+// K/V pages double-buffered in LDS; what LlamaModel prefill runs).
 #include "common.h"
 
 #define QSA_PAGE 64
 
 using bf16x8_a = __attribute__((ext_vector_type(8))) short;
 using f32x4_a = __attribute__((ext_vector_type(4))) float;
+using u32x4_a = __attribute__((ext_vector_type(4))) unsigned int;
 
 template <int D>
 __global__ void __launch_bounds__(256)
@@ -625,4 +634,500 @@ extern "C" void qsa_paged_attn_prefill_launch(
   QSA_PREFILL_CASE(128, true) QSA_PREFILL_CASE(128, false)
   QSA_PREFILL_CASE(64, true) QSA_PREFILL_CASE(64, false)
 #undef QSA_PREFILL_CASE
+}
+
+// ---------------------------------------------------------------------------
+// TILED varlen flash prefill: the same arithmetic as qsa_paged_attn_prefill,
+// row for row and bit for bit, with each K/V page fetched from global memory
+// ONCE per workgroup and shared through LDS.
+//
+// Workgroup = 256 threads = one tile of ROWS q rows of one item x 4
+// consecutive q heads (wave = head; at R % 4 == 0 all four share one kv
+// head).  Each wave owns S = ROWS/16 sub-tiles of 16 rows: a K or V
+// fragment is read from LDS once and feeds the MFMAs of all S sub-tiles,
+// so the per-page fragment traffic drops from 4 x 32 KiB of global loads
+// to one 32 KiB cooperative copy plus S-fold reuse of every ds_read_b128.
+//
+// Pipeline: the (page, kv head) K block and V^T block are each D*128 bytes
+// contiguous in the cache.  All 256 threads copy page i+1 into registers
+// (16 B per lane and load) before computing page i out of LDS buffer i&1,
+// then write the registers into buffer (i+1)&1; ONE barrier per page
+// separates "everyone finished reading buffer i&1 and writing the other"
+// from the next iteration.  2 buffers x (K + V) = D*512 bytes: 64 KiB at
+// D=128, two workgroups per CU.
+//
+// LDS images, in 16-byte slots (bank = slot mod 16 for ds_read_b128, lanes
+// conflict only inside the instruction's four 16-lane groups, each of
+// which holds 8 lanes of one hi value and 8 of the next, covering all 16
+// col values exactly once):
+//   K: copied LINEAR.  The A-fragment read takes slot (ks*4+hi)*64 +
+//      pt*16 + col, i.e. slot mod 16 == col: the 16 lanes of a group hit 16
+//      different slots -> conflict-free as stored, no padding needed.
+//   V^T: row d holds 8 slots (128 B pitch); the B-fragment read takes slot
+//      s = half*4 + hi of row d = dt*16 + col, so linear storage gives
+//      slot mod 16 = (col&1)*8 + half*4 + hi: 4 distinct values per group,
+//      a 4-way conflict.  Stored XOR-swizzled, slot s of row d lives at
+//      d*8 + (s ^ ((d>>1)&7)).  Inside a group hi takes two adjacent values
+//      {2g, 2g+1} on col sets whose (col>>1) values are {0,1,6,7} and
+//      {2,3,4,5}; XOR with s maps them onto disjoint halves of 0..7, and
+//      (col&1) picks the upper or lower 8 slots -> 16 distinct slots,
+//      conflict-free.
+//
+// Bit-exactness against the one-wave-per-block kernel: a sub-tile keeps its
+// own horizon (max_abs), processes exactly the pages the old kernel would
+// (pi < its own page count, and the same wave-uniform "whole page masked"
+// skip), and every accumulator sees the same MFMA/VALU sequence: the same
+// ks order, mask, scale, __expf, alpha, psum order, P packing shuffles, PV
+// order (half, then dt) and epilogue.
+// ---------------------------------------------------------------------------
+template <int D, bool CAUSAL, int ROWS>
+__global__ void __launch_bounds__(256, ROWS == 32 ? 2 : 1)
+qsa_paged_attn_prefill_tiled(
+    const unsigned short* __restrict__ q,   // [T, QH, D] strided
+    const unsigned short* __restrict__ kc,
+    const unsigned short* __restrict__ vc,
+    const int* __restrict__ block_table,    // [nb, npmax]
+    const int* __restrict__ tile_item,      // [NT]
+    const int* __restrict__ tile_pos0,      // [NT] first new-row of the tile
+    const int* __restrict__ item_off,       // [nb] row offset
+    const int* __restrict__ item_start,     // [nb] cached
+    const int* __restrict__ item_len,       // [nb] new rows
+    unsigned short* __restrict__ out,       // [T, QH*D]
+    float scale, int NT, int QH, int KVH, int npmax, long long qstride) {
+  constexpr int S = ROWS / 16;            // sub-tiles per wave
+  constexpr int KSTEPS = D / 32;
+  constexpr int DTILES = D / 16;
+  constexpr int SLOTS = D * 8;            // 16-B slots per K (or V) page
+  constexpr int LD = SLOTS / 256;         // slots per thread and image
+  __shared__ u32x4_a lds[2][2][SLOTS];      // [buffer][K, V][slot]
+
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = tid >> 6;
+  const int HG = QH >> 2;                 // 4-head groups
+  const int tile = blockIdx.x / HG;
+  const int hg = blockIdx.x % HG;
+  const int qh = hg * 4 + wave;
+  const int R = QH / KVH;
+  const int kvh = (hg * 4) / R;
+  const int item = tile_item[tile];
+  const int tpos0 = tile_pos0[tile];
+  const int n_i = item_len[item];
+  const int start = item_start[item];
+  const int off = item_off[item];
+  const int col = lane & 15;
+  const int hi = lane >> 4;
+
+  // ---- per-sub-tile state ------------------------------------------------
+  bf16x8_a qf[S][KSTEPS];
+  float m[S], lsum[S];
+  f32x4_a o_acc[S][DTILES];
+  int max_abs[S], npg[S];
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int pos0 = tpos0 + 16 * s;
+    const int qrow_l = max(min(pos0 + col, n_i - 1), 0);   // clamp pad rows
+    const unsigned short* qrow =
+        q + (long long)(off + qrow_l) * qstride + (long long)qh * D;
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+      qf[s][ks] = *reinterpret_cast<const bf16x8_a*>(qrow + ks * 32 + hi * 8);
+    m[s] = -3.0e38f;
+    lsum[s] = 0.f;
+#pragma unroll
+    for (int dt = 0; dt < DTILES; ++dt)
+      o_acc[s][dt] = (f32x4_a){0.f, 0.f, 0.f, 0.f};
+    max_abs[s] = CAUSAL ? start + min(pos0 + 15, n_i - 1) : start + n_i - 1;
+    // a sub-tile past the item's end has no rows: it walks no page
+    npg[s] = (pos0 < n_i) ? (max_abs[s] + QSA_PAGE) / QSA_PAGE : 0;
+  }
+  // the workgroup walks pages up to its last live sub-tile's horizon
+  const int wg_abs = CAUSAL ? start + min(tpos0 + ROWS - 1, n_i - 1)
+                            : start + n_i - 1;
+  const int np_wg = (tpos0 < n_i) ? (wg_abs + QSA_PAGE) / QSA_PAGE : 0;
+  const int* btab = block_table + (long long)item * npmax;
+
+  // page copy, 16 B per lane and load: global -> registers (QSA_FETCH),
+  // registers -> LDS buffer (QSA_STASH; V^T slot swizzled, see above)
+  u32x4_a kreg[LD], vreg[LD];
+#define QSA_FETCH(PI)                                                      \
+  {                                                                        \
+    const long long pbase = ((long long)btab[PI] * KVH + kvh) * SLOTS;     \
+    const u32x4_a* kp = reinterpret_cast<const u32x4_a*>(kc) + pbase;          \
+    const u32x4_a* vp = reinterpret_cast<const u32x4_a*>(vc) + pbase;          \
+    _Pragma("unroll") for (int i = 0; i < LD; ++i) {                       \
+      kreg[i] = kp[tid + 256 * i];                                         \
+      vreg[i] = vp[tid + 256 * i];                                         \
+    }                                                                      \
+  }
+#define QSA_STASH(BUF)                                                     \
+  {                                                                        \
+    _Pragma("unroll") for (int i = 0; i < LD; ++i) {                       \
+      const int g = tid + 256 * i;                                         \
+      const int d = g >> 3;                                                \
+      lds[BUF][0][g] = kreg[i];                                            \
+      lds[BUF][1][d * 8 + ((g & 7) ^ ((d >> 1) & 7))] = vreg[i];           \
+    }                                                                      \
+  }
+
+  if (np_wg > 0) {
+    QSA_FETCH(0)
+    QSA_STASH(0)
+  }
+  __syncthreads();
+
+  const int vsw = (col >> 1) & 7;          // V^T swizzle of this lane's rows
+  for (int pi = 0; pi < np_wg; ++pi) {
+    const int buf = pi & 1;
+    const bool more = pi + 1 < np_wg;
+    if (more) QSA_FETCH(pi + 1)
+    const u32x4_a* ldsK = lds[buf][0];
+    const u32x4_a* ldsV = lds[buf][1];
+
+    bool act[S];
+#pragma unroll
+    for (int s = 0; s < S; ++s) act[s] = pi < npg[s];
+
+    // ---- scores: one K fragment read feeds all live sub-tiles ----------
+    f32x4_a sc[S][4];
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt) {
+#pragma unroll
+      for (int s = 0; s < S; ++s) sc[s][pt] = (f32x4_a){0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks) {
+        const bf16x8_a kf = __builtin_bit_cast(
+            bf16x8_a, ldsK[(ks * 4 + hi) * QSA_PAGE + pt * 16 + col]);
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+          if (act[s])
+            sc[s][pt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                kf, qf[s][ks], sc[s][pt], 0, 0, 0);
+      }
+    }
+
+    // ---- online softmax per sub-tile (lifted from the old kernel) -------
+    bool pv[S];
+    bf16x8_a pa[S][2];
+#pragma unroll
+    for (int s = 0; s < S; ++s) {
+      pv[s] = false;
+      if (!act[s]) continue;
+      const int pos0 = tpos0 + 16 * s;
+      const int nvalid = min(max_abs[s] + 1 - pi * QSA_PAGE, QSA_PAGE);
+      const int qabs = start + pos0 + col;
+      float pagemax = -3.0e38f;
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int kpos = pt * 16 + hi * 4 + r;
+          const int kabs = pi * QSA_PAGE + kpos;
+          const bool ok = (kpos < nvalid) && (!CAUSAL || kabs <= qabs) &&
+                          (pos0 + col < n_i);
+          float v = ok ? sc[s][pt][r] * scale : -3.0e38f;
+          sc[s][pt][r] = v;
+          pagemax = fmaxf(pagemax, v);
+        }
+      }
+      pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 16, QSA_WAVE));
+      pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 32, QSA_WAVE));
+      // wave-uniform skip of a page masked for EVERY column, as before
+      if (__all(pagemax <= -3.0e38f)) continue;
+      pv[s] = true;
+      const float m_new = fmaxf(m[s], pagemax);
+      float alpha = __expf(m[s] - m_new);
+      if (m[s] <= -3.0e38f) alpha = 0.f;
+      m[s] = m_new;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const float alpha_r = __shfl(alpha, hi * 4 + r, 16);
+#pragma unroll
+        for (int dt = 0; dt < DTILES; ++dt) o_acc[s][dt][r] *= alpha_r;
+      }
+      unsigned int ppk[8];
+      float psum = 0.f;
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt) {
+        float p0f = 0.f, p1f = 0.f, p2f = 0.f, p3f = 0.f;
+        if (sc[s][pt][0] > -1.0e38f) p0f = __expf(sc[s][pt][0] - m_new);
+        if (sc[s][pt][1] > -1.0e38f) p1f = __expf(sc[s][pt][1] - m_new);
+        if (sc[s][pt][2] > -1.0e38f) p2f = __expf(sc[s][pt][2] - m_new);
+        if (sc[s][pt][3] > -1.0e38f) p3f = __expf(sc[s][pt][3] - m_new);
+        psum += p0f + p1f + p2f + p3f;
+        ppk[pt * 2] = f32x2_to_bf16x2(p0f, p1f);
+        ppk[pt * 2 + 1] = f32x2_to_bf16x2(p2f, p3f);
+      }
+      psum += __shfl_xor(psum, 16, QSA_WAVE);
+      psum += __shfl_xor(psum, 32, QSA_WAVE);
+      lsum[s] = lsum[s] * alpha + psum;
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int src_a = col + (((2 * hi) & 3) << 4);
+        const int src_b = col + (((2 * hi + 1) & 3) << 4);
+        const int tA = half * 2;
+        const int tB = half * 2 + 1;
+        const unsigned int a0A = __shfl(ppk[tA * 2], src_a, QSA_WAVE);
+        const unsigned int a1A = __shfl(ppk[tA * 2 + 1], src_a, QSA_WAVE);
+        const unsigned int b0A = __shfl(ppk[tA * 2], src_b, QSA_WAVE);
+        const unsigned int b1A = __shfl(ppk[tA * 2 + 1], src_b, QSA_WAVE);
+        const unsigned int a0B = __shfl(ppk[tB * 2], src_a, QSA_WAVE);
+        const unsigned int a1B = __shfl(ppk[tB * 2 + 1], src_a, QSA_WAVE);
+        const unsigned int b0B = __shfl(ppk[tB * 2], src_b, QSA_WAVE);
+        const unsigned int b1B = __shfl(ppk[tB * 2 + 1], src_b, QSA_WAVE);
+        const bool lo = hi < 2;
+        const u32x4_a pu = {lo ? a0A : a0B, lo ? a1A : a1B,
+                            lo ? b0A : b0B, lo ? b1A : b1B};
+        pa[s][half] = __builtin_bit_cast(bf16x8_a, pu);
+      }
+    }
+
+    // ---- PV: one V^T fragment read feeds all live sub-tiles -------------
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+#pragma unroll
+      for (int dt = 0; dt < DTILES; ++dt) {
+        const bf16x8_a vf = __builtin_bit_cast(
+            bf16x8_a, ldsV[(dt * 16 + col) * 8 + ((half * 4 + hi) ^ vsw)]);
+#pragma unroll
+        for (int s = 0; s < S; ++s)
+          if (pv[s])
+            o_acc[s][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                pa[s][half], vf, o_acc[s][dt], 0, 0, 0);
+      }
+    }
+
+    if (more) QSA_STASH(buf ^ 1)
+    __syncthreads();
+  }
+
+#undef QSA_FETCH
+#undef QSA_STASH
+
+  // ---- epilogue per sub-tile (as the old kernel) --------------------------
+#pragma unroll
+  for (int s = 0; s < S; ++s) {
+    const int pos0 = tpos0 + 16 * s;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int qr = hi * 4 + r;
+      const float lr = __shfl(lsum[s], qr, 16);
+      const float inv = (lr > 0.f) ? 1.f / lr : 0.f;
+      if (pos0 + qr < n_i) {
+        unsigned short* orow = out +
+            (long long)(off + pos0 + qr) * (QH * D) + (long long)qh * D;
+#pragma unroll
+        for (int dt = 0; dt < DTILES; ++dt)
+          orow[dt * 16 + col] = f32_to_bf16(o_acc[s][dt][r] * inv);
+      }
+    }
+  }
+}
+
+// rows: q rows per workgroup tile (32; 64 at D=64 only).  Returns 0 when the
+// GQA ratio is not covered (the binding then runs the one-wave-per-block
+// kernel).
+extern "C" int qsa_paged_attn_prefill_tiled_launch(
+    const unsigned short* q, const unsigned short* kc,
+    const unsigned short* vc, const int* block_table, const int* tile_item,
+    const int* tile_pos0, const int* item_off, const int* item_start,
+    const int* item_len, unsigned short* out, float scale, int NT, int QH,
+    int KVH, int npmax, int D, long long qstride, int causal, int rows,
+    hipStream_t stream) {
+  if (KVH <= 0 || QH % KVH != 0 || (QH / KVH) % 4 != 0) return 0;
+  if (NT <= 0) return 1;
+  dim3 grid((unsigned)((long long)NT * (QH / 4)));
+#define QSA_TILED_CASE(DD, CC, RR)                                         \
+  if (D == DD && causal == (int)CC && rows == RR) {                        \
+    hipLaunchKernelGGL((qsa_paged_attn_prefill_tiled<DD, CC, RR>), grid,   \
+                       dim3(256), 0, stream, q, kc, vc, block_table,       \
+                       tile_item, tile_pos0, item_off, item_start,         \
+                       item_len, out, scale, NT, QH, KVH, npmax, qstride); \
+    return 1;                                                              \
+  }
+  // D=128 with 64 rows needs 4 x 32 accumulator + 64 Q + 64 score
+  // registers per lane on top of the 32 staging registers and spills even
+  // at one wave per SIMD, so it is not instantiated
+  QSA_TILED_CASE(128, true, 32) QSA_TILED_CASE(128, false, 32)
+  QSA_TILED_CASE(64, true, 32) QSA_TILED_CASE(64, false, 32)
+  QSA_TILED_CASE(64, true, 64) QSA_TILED_CASE(64, false, 64)
+#undef QSA_TILED_CASE
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Fused PREFILL RoPE + KV scatter (the prefill twin of qsa_rope_kv_append).
+//
+// One launch, two kinds of 256-thread block:
+//   q blocks   rotate q in place over ALL rows passed (pad rows included).
+//              A thread owns 8 consecutive dims and their +D/2 partners:
+//              two 16-byte loads, two 16-byte stores, lanes along d.
+//   kv blocks  take 64 consecutive tokens of one kv head.  k is rotated and
+//              written ONLY to the cache (nothing reads rotated k from the
+//              qkv buffer: prefill attention reads the cache).  In the K
+//              layout [page, kvh, D/8, 64, 8] a token's 8 consecutive dims
+//              are one 16-byte store, and lanes run along the tokens, so
+//              consecutive slots give consecutive 16-byte stores.  v is
+//              transposed through LDS and stored with lanes along the
+//              tokens too: for a run of consecutive slots a wave writes one
+//              contiguous run of the V^T row per d, where qsa_kv_scatter
+//              wrote 64 different cache lines per wave store.  The stores
+//              are per element and each goes through its own slot id, so
+//              ANY slot pattern (page crossings, item boundaries,
+//              permutations) is correct with no special case; only the
+//              coalescing depends on the slots being consecutive.
+// Rows >= T (pad rows) never touch the cache.  Rotation expressions are the
+// ones of qsa_rope_kernel, so results are bit-identical to rope_inplace
+// followed by kv_scatter.
+// ---------------------------------------------------------------------------
+#define QSA_RKS_TOK 64
+template <int D>
+__global__ void __launch_bounds__(256)
+qsa_rope_kv_scatter(unsigned short* __restrict__ q,        // [Tq, QH, D]
+                    const unsigned short* __restrict__ k,  // [>=T, KVH, D]
+                    const unsigned short* __restrict__ v,
+                    unsigned short* __restrict__ kc,
+                    unsigned short* __restrict__ vc,
+                    const float* __restrict__ cos_t,
+                    const float* __restrict__ sin_t,
+                    const int* __restrict__ pos,           // [Tq]
+                    const int* __restrict__ slots,         // [T]
+                    int Tq, int T, int QH, int KVH, int nqblocks,
+                    long long qstride, long long kvstride) {
+  constexpr int half = D / 2;
+  constexpr int JD = D / 16;                // 8-dim groups per half
+  constexpr int VP = D / 2 + 1;             // LDS row pitch in dwords (odd)
+  __shared__ unsigned int vt[QSA_RKS_TOK * VP];
+  const int tid = threadIdx.x;
+
+  if ((int)blockIdx.x < nqblocks) {
+    // ---- q: (token, head, j) units, j fastest ---------------------------
+    const long long u = (long long)blockIdx.x * 256 + tid;
+    const long long unit = u / JD;
+    const int j = (int)(u % JD);
+    const long long t = unit / QH;
+    const int h = (int)(unit % QH);
+    if (t >= Tq) return;
+    unsigned short* base = q + t * qstride + (long long)h * D + j * 8;
+    const long long toff = (long long)pos[t] * half + j * 8;
+    float c[8], s[8];
+    *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cos_t + toff);
+    *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cos_t + toff + 4);
+    *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sin_t + toff);
+    *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sin_t + toff + 4);
+    uint4 a = *reinterpret_cast<const uint4*>(base);
+    uint4 b = *reinterpret_cast<const uint4*>(base + half);
+    unsigned int* au = reinterpret_cast<unsigned int*>(&a);
+    unsigned int* bu = reinterpret_cast<unsigned int*>(&b);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float2 x0 = bf16x2_to_f32x2(au[e]);
+      const float2 x1 = bf16x2_to_f32x2(bu[e]);
+      const float c0 = c[2 * e], c1 = c[2 * e + 1];
+      const float s0 = s[2 * e], s1 = s[2 * e + 1];
+      au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
+              ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
+      bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
+              ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
+    }
+    *reinterpret_cast<uint4*>(base) = a;
+    *reinterpret_cast<uint4*>(base + half) = b;
+    return;
+  }
+
+  // ---- k/v: 64 tokens of one kv head -------------------------------------
+  const int kb = blockIdx.x - nqblocks;
+  const int kvh = kb % KVH;
+  const long long t0 = (long long)(kb / KVH) * QSA_RKS_TOK;
+  const int nt = (int)min((long long)QSA_RKS_TOK, (long long)T - t0);
+
+  // v rows -> LDS, 16-byte global loads with lanes along d
+#pragma unroll
+  for (int i = 0; i < QSA_RKS_TOK * (D / 8) / 256; ++i) {
+    const int item = tid + 256 * i;
+    const int tl = item / (D / 8);
+    const int dg = item % (D / 8);
+    if (tl < nt) {
+      const uint4 x = *reinterpret_cast<const uint4*>(
+          v + (t0 + tl) * kvstride + (long long)kvh * D + dg * 8);
+      unsigned int* dst = vt + tl * VP + dg * 4;
+      dst[0] = x.x; dst[1] = x.y; dst[2] = x.z; dst[3] = x.w;
+    }
+  }
+
+  // k: rotate 8 dims + partners per thread, lanes along the tokens
+#pragma unroll
+  for (int i = 0; i < QSA_RKS_TOK * JD / 256; ++i) {
+    const int item = tid + 256 * i;
+    const int tl = item % QSA_RKS_TOK;
+    const int j = item / QSA_RKS_TOK;
+    if (tl < nt) {
+      const long long t = t0 + tl;
+      const unsigned short* base = k + t * kvstride + (long long)kvh * D + j * 8;
+      const long long toff = (long long)pos[t] * half + j * 8;
+      float c[8], s[8];
+      *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cos_t + toff);
+      *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cos_t + toff + 4);
+      *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sin_t + toff);
+      *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sin_t + toff + 4);
+      uint4 a = *reinterpret_cast<const uint4*>(base);
+      uint4 b = *reinterpret_cast<const uint4*>(base + half);
+      unsigned int* au = reinterpret_cast<unsigned int*>(&a);
+      unsigned int* bu = reinterpret_cast<unsigned int*>(&b);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float2 x0 = bf16x2_to_f32x2(au[e]);
+        const float2 x1 = bf16x2_to_f32x2(bu[e]);
+        const float c0 = c[2 * e], c1 = c[2 * e + 1];
+        const float s0 = s[2 * e], s1 = s[2 * e + 1];
+        au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
+                ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
+        bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
+                ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
+      }
+      const int slot = slots[t];
+      const long long page = slot / QSA_PAGE;
+      const int pin = slot % QSA_PAGE;
+      unsigned short* kdst =
+          kc + ((((page * KVH + kvh) * (D / 8) + j) * QSA_PAGE) + pin) * 8;
+      *reinterpret_cast<uint4*>(kdst) = a;
+      *reinterpret_cast<uint4*>(kdst + (long long)(half / 8) * QSA_PAGE * 8) = b;
+    }
+  }
+
+  __syncthreads();
+
+  // v: transposed store, lanes along the tokens
+  const unsigned short* vt16 = reinterpret_cast<const unsigned short*>(vt);
+  const int tl = tid % QSA_RKS_TOK;
+  if (tl < nt) {
+    const int slot = slots[t0 + tl];
+    const long long page = slot / QSA_PAGE;
+    const int pin = slot % QSA_PAGE;
+    unsigned short* vdst = vc + ((page * KVH + kvh) * D) * QSA_PAGE + pin;
+#pragma unroll 8
+    for (int d = tid / QSA_RKS_TOK; d < D; d += 256 / QSA_RKS_TOK)
+      vdst[(long long)d * QSA_PAGE] = vt16[tl * (VP * 2) + d];
+  }
+}
+
+extern "C" void qsa_rope_kv_scatter_launch(
+    unsigned short* q, const unsigned short* k, const unsigned short* v,
+    unsigned short* kc, unsigned short* vc, const float* cos_t,
+    const float* sin_t, const int* pos, const int* slots, int Tq, int T,
+    int QH, int KVH, int D, long long qstride, long long kvstride,
+    hipStream_t stream) {
+  const long long qthreads = (long long)Tq * QH * (D / 16);
+  const int nqblocks = (int)((qthreads + 255) / 256);
+  const int nkvblocks = ((T + QSA_RKS_TOK - 1) / QSA_RKS_TOK) * KVH;
+  if (nqblocks + nkvblocks == 0) return;
+  dim3 grid(nqblocks + nkvblocks);
+  if (D == 128)
+    hipLaunchKernelGGL((qsa_rope_kv_scatter<128>), grid, dim3(256), 0, stream,
+                       q, k, v, kc, vc, cos_t, sin_t, pos, slots, Tq, T, QH,
+                       KVH, nqblocks, qstride, kvstride);
+  else if (D == 64)
+    hipLaunchKernelGGL((qsa_rope_kv_scatter<64>), grid, dim3(256), 0, stream,
+                       q, k, v, kc, vc, cos_t, sin_t, pos, slots, Tq, T, QH,
+                       KVH, nqblocks, qstride, kvstride);
 }
