@@ -9,10 +9,15 @@ synthetic data / random weights; the architecture is the named config).
 
 Decode path (the hot path): fully fused per layer —
   rmsnorm_residual -> qkv (weight-streaming skinny GEMM or rocBLAS by
-  measured winner per shape) -> fused rope+paged-KV-append ->
-  MFMA flash-decode paged attention -> o GEMM -> rmsnorm_residual ->
-  gate_up GEMM -> swiglu -> down GEMM; the whole step is hipGraph-captured
-  and self-feeding (models/serve.py).
+  measured winner per shape) -> ONE decode-attention launch (rope on q in
+  registers, rope + paged-KV append of the new k/v row, pipelined MFMA
+  flash-decode over the paged cache, split merge in the workgroup; see
+  qsa_paged_attn_mfma_fused in ops/hip/paged_attn.hip) -> o GEMM ->
+  rmsnorm_residual -> gate_up GEMM -> swiglu -> down GEMM; the whole step
+  is hipGraph-captured and self-feeding (models/serve.py).
+  QSA_DECODE_V1=1 restores the earlier three kernels (rope+append,
+  attention with fp32 partials, split reduce), which the fused launch
+  matches bit for bit.
 Prefill: fused per-token projections over the varlen concatenation, then
 ONE varlen flash-attention kernel per layer streaming K/V straight from
 the paged cache (ops/hip/paged_attn.hip); the CPU test path keeps a
@@ -46,6 +51,10 @@ from .kv_cache import PagedKVCache
 # (rope_inplace + kv_scatter + one-wave-per-q-block attention) for A/B runs;
 # tests flip the module attribute.
 PREFILL_V1 = os.environ.get("QSA_PREFILL_V1") == "1"
+# QSA_DECODE_V1=1 (read once, here) restores the three-kernel decode
+# attention (rope_kv_append + paged_attn_decode, whose second half is the
+# split-merge kernel) for A/B runs; tests flip the module attribute.
+DECODE_V1 = os.environ.get("QSA_DECODE_V1") == "1"
 # q rows per workgroup of the tiled prefill attention kernel
 PREFILL_TILE_ROWS = 32
 
@@ -293,10 +302,19 @@ class LlamaModel:
             q = qkv[:, :qd].view(B, self.n_q, c.d_head)
             k = qkv[:, qd:qd + kd].view(B, self.n_kv, c.d_head)
             v = qkv[:, qd + kd:].view(B, self.n_kv, c.d_head)
-            D.rope_kv_append(q, k, v, kv.k[li], kv.v[li], self.rope_cos,
-                             self.rope_sin, block_table, seq_lens)
-            attn = D.paged_attn_decode(q, kv.k[li], kv.v[li], block_table,
-                                       seq_lens, self.scale)
+            if q.is_cuda and c.d_head in (64, 128) and not DECODE_V1:
+                # one launch: rope + append + attention + split merge
+                attn = D.decode_attn_fused(q, k, v, kv.k[li], kv.v[li],
+                                           self.rope_cos, self.rope_sin,
+                                           block_table, seq_lens,
+                                           self.scale)
+            else:
+                D.rope_kv_append(q, k, v, kv.k[li], kv.v[li],
+                                 self.rope_cos, self.rope_sin, block_table,
+                                 seq_lens)
+                attn = D.paged_attn_decode(q, kv.k[li], kv.v[li],
+                                           block_table, seq_lens,
+                                           self.scale)
             o = self._tp_all_reduce(
                 self._linear(attn.view(B, -1), L["wo"], L.get("wo_f"),
                              L.get("wo_f8")))

@@ -177,6 +177,25 @@ def paged_attn_decode(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
                           scale).to(q.dtype)
 
 
+def decode_attn_fused(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                      kc: torch.Tensor, vc: torch.Tensor,
+                      cos_t: torch.Tensor, sin_t: torch.Tensor,
+                      block_table: torch.Tensor, seq_lens: torch.Tensor,
+                      scale: float) -> torch.Tensor:
+    """One decode step's attention in a single launch: rope(q, k) at
+    position seq_lens-1, append of the rotated k (+v) to the paged cache,
+    paged attention and the split merge.  Bit-identical to rope_kv_append
+    followed by paged_attn_decode.  The fused kernel rotates q in
+    registers and leaves q/k/v untouched (nothing reads them afterwards);
+    the CPU reference composes the two reference ops and so rotates q and
+    k in place."""
+    if _cuda(q):
+        return ext().decode_attn_fused(q, k, v, kc, vc, cos_t, sin_t,
+                                       block_table, seq_lens, scale)
+    rope_kv_append(q, k, v, kc, vc, cos_t, sin_t, block_table, seq_lens)
+    return paged_attn_decode(q, kc, vc, block_table, seq_lens, scale)
+
+
 # ---- skinny decode GEMM ---------------------------------------------------
 
 def can_pack_weight(n: int, k: int) -> bool:

@@ -42,6 +42,11 @@ extern "C" void qsa_paged_attn_mfma_launch(
     const unsigned short*, const unsigned short*, const unsigned short*,
     const int*, const int*, float*, float*, unsigned short*, float, int, int,
     int, int, int, long long, int, hipStream_t);
+extern "C" void qsa_paged_attn_mfma_fused_launch(
+    const unsigned short*, const unsigned short*, const unsigned short*,
+    unsigned short*, unsigned short*, const float*, const float*, const int*,
+    const int*, float*, float*, unsigned short*, float, int, int, int, int,
+    int, long long, long long, int, int, hipStream_t);
 extern "C" void qsa_kv_append_launch(const unsigned short*,
                                      const unsigned short*, unsigned short*,
                                      unsigned short*, const int*, const int*,
@@ -237,6 +242,82 @@ torch::Tensor paged_attn_decode(torch::Tensor q, torch::Tensor kc,
       seq_lens.data_ptr<int>(), part_o.data_ptr<float>(),
       part_ml.data_ptr<float>(), u16m(out), (float)scale, B, QH, KVH,
       max_pages, D, q.stride(0), ns, cur_stream());
+  return out;
+}
+
+// Flash-decoding split count, derived exactly as paged_attn_decode derives
+// it: it fixes the split boundaries and with them the rounding, so the two
+// must never drift apart (tests/test_gpu_decode_fused.py compares bits).
+static int decode_num_splits(int B, int KVH, int max_pages) {
+  int ns = (int)std::min<long long>(32, std::max<long long>(
+      1, (2048 + (long long)B * KVH - 1) / ((long long)B * KVH)));
+  if (ns > 1) ns = std::max(ns, 4);   // fill all 4 waves per workgroup
+  return std::min(ns, std::max(1, max_pages));
+}
+
+// One launch for a decode step's attention: RoPE on q (in registers) and on
+// the new k row, k/v append to the paged cache, pipelined flash-decode and
+// the split merge.  q/k/v are the UN-rotated strided views of the qkv
+// buffer and stay untouched.  Bit-identical to rope_kv_append followed by
+// paged_attn_decode.  waves_per_simd picks the register budget the kernel
+// was compiled for (1 or 2).
+torch::Tensor decode_attn_fused(torch::Tensor q, torch::Tensor k,
+                                torch::Tensor v, torch::Tensor kc,
+                                torch::Tensor vc, torch::Tensor cos_t,
+                                torch::Tensor sin_t,
+                                torch::Tensor block_table,
+                                torch::Tensor seq_lens, double scale,
+                                int64_t waves_per_simd) {
+  CHK_DEV(q); CHK_BF16(q); CHK_BF16(k); CHK_BF16(v); CHK_BF16(kc);
+  CHK_BF16(vc); CHK_CONT(kc); CHK_CONT(vc); CHK_F32(cos_t); CHK_F32(sin_t);
+  CHK_CONT(cos_t); CHK_CONT(sin_t); CHK_I32(block_table); CHK_I32(seq_lens);
+  CHK_CONT(block_table);
+  const int B = q.size(0), QH = q.size(1), D = q.size(2);
+  const int KVH = kc.size(1);
+  chk_hd_strided(q, D, "q"); chk_hd_strided(k, D, "k");
+  chk_hd_strided(v, D, "v");
+  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v strides must match");
+  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(1) == KVH &&
+              v.size(1) == KVH && k.size(2) == D && v.size(2) == D,
+              "k/v must be [B, KVH, D]");
+  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
+  TORCH_CHECK(QH % KVH == 0, "GQA requires QH % KVH == 0");
+  TORCH_CHECK(QH / KVH <= 16, "GQA ratio <= 16");
+  TORCH_CHECK(kc.size(2) == D / 8 && kc.size(3) == 64 && kc.size(4) == 8,
+              "K cache layout [P, KVH, D/8, 64, 8]");
+  TORCH_CHECK(vc.size(2) == D && vc.size(3) == 64,
+              "V cache layout [P, KVH, D, 64] (transposed)");
+  TORCH_CHECK(cos_t.size(1) == D / 2 && sin_t.size(1) == D / 2,
+              "rope tables must be [positions, D/2]");
+  // 16-byte fragment loads of q/k/v rows
+  TORCH_CHECK(q.stride(0) % 8 == 0 && k.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(k.data_ptr()) % 16 == 0,
+              "q/k rows must be 16-byte aligned");
+  TORCH_CHECK(waves_per_simd == 1 || waves_per_simd == 2,
+              "waves_per_simd must be 1 or 2");
+  TORCH_CHECK(seq_lens.numel() == B && block_table.size(0) == B,
+              "one seq_len / block-table row per sequence");
+  const int max_pages = block_table.size(1);
+  auto out = torch::empty({B, QH, D}, q.options());
+  const int ns = decode_num_splits(B, KVH, max_pages);
+  // NS <= 4 merges inside the workgroup: no partial buffers at all
+  torch::Tensor part_o, part_ml;
+  float* po = nullptr;
+  float* pml = nullptr;
+  if (ns > 4) {
+    auto opts_f = q.options().dtype(at::kFloat);
+    part_o = torch::empty({B, QH, ns, D}, opts_f);
+    part_ml = torch::empty({B, QH, ns, 2}, opts_f);
+    po = part_o.data_ptr<float>();
+    pml = part_ml.data_ptr<float>();
+  }
+  qsa_paged_attn_mfma_fused_launch(
+      u16(q), u16(k), u16(v), u16m(kc), u16m(vc), cos_t.data_ptr<float>(),
+      sin_t.data_ptr<float>(), block_table.data_ptr<int>(),
+      seq_lens.data_ptr<int>(), po, pml, u16m(out), (float)scale, B, QH, KVH,
+      max_pages, D, q.stride(0), k.stride(0), ns, (int)waves_per_simd,
+      cur_stream());
   return out;
 }
 
@@ -621,6 +702,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "varlen flash prefill attention over the paged cache");
   m.def("paged_attn_decode", &paged_attn_decode,
         "paged-attention decode (bf16, GQA, page=64)");
+  m.def("decode_attn_fused", &decode_attn_fused,
+        "fused decode step: rope + kv append + paged attention + split merge",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("kc"),
+        py::arg("vc"), py::arg("cos_t"), py::arg("sin_t"),
+        py::arg("block_table"), py::arg("seq_lens"), py::arg("scale"),
+        py::arg("waves_per_simd") = 2);
   m.def("kv_append", &kv_append, "append one step's k/v to the paged cache");
   m.def("paged_attn_prefill_tiled", &paged_attn_prefill_tiled,
         "varlen flash prefill attention, K/V pages shared through LDS");

@@ -20,6 +20,12 @@
 //     per-head VALU design re-read it R times.
 //   - Context splits fill the chip (grid = B*KVH*NS >= ~2k waves);
 //     unnormalized partials (o, m, l) merge in qsa_attn_reduce.
+//   - What the model runs is qsa_paged_attn_mfma_fused: this decomposition
+//     and arithmetic, bit for bit, with RoPE and the KV append folded in,
+//     the page's K/V fragment loads issued in batches one stage ahead of
+//     the MFMAs that consume them, and the splits merged inside the
+//     workgroup when NS <= 4.  qsa_rope_kv_append + qsa_paged_attn_mfma +
+//     qsa_attn_reduce remain as its oracle (QSA_DECODE_V1=1 runs them).
 //
 // The online softmax runs per head-column in registers: column max/sum
 // reduce with two shfl_xor hops (the 4 hi-lane groups of a column).
@@ -280,6 +286,433 @@ extern "C" void qsa_paged_attn_mfma_launch(
     hipLaunchKernelGGL((qsa_attn_reduce<64>), dim3(B * QH), dim3(64), 0,
                        stream, part_o, part_ml, out, NS);
   }
+}
+
+__device__ __forceinline__ float qsa_bperm_f(int byte_addr, float v) {
+  return __builtin_bit_cast(
+      float, __builtin_amdgcn_ds_bpermute(byte_addr, __builtin_bit_cast(int, v)));
+}
+__device__ __forceinline__ unsigned int qsa_bperm_u(int byte_addr,
+                                                   unsigned int v) {
+  return (unsigned int)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
+}
+
+// One page of the fused decode loop.  PREFETCH is compile-time so that each
+// instantiation is straight-line code: with a runtime "is there a next
+// page" branch around the K loads the compiler's wait-count bookkeeping
+// merges both paths and makes PV wait for the prefetched K as well.
+template <int D, bool PREFETCH>
+__device__ __forceinline__ void qsa_decode_page(
+    const unsigned short* kc, const unsigned short* vc, const int* btab,
+    int pi, int p1, int seqlen, int KVH, int kvh, int koff, int voff,
+    int col, int hi, float scale, int& page, int& page_n,
+    const bf16x8_a (&qf)[D / 32], bf16x8_a (&kfr)[4][D / 32],
+    bf16x8_a (&vfr)[2][D / 16], f32x4_a (&o_acc)[D / 16], float& m,
+    float& lsum) {
+  constexpr int KSTEPS = D / 32;
+  constexpr int DTILES = D / 16;
+  // lane shuffles as bare ds_bpermute on byte addresses (lane * 4): the
+  // same data movement as __shfl/__shfl_xor without their per-call range
+  // check, which costs VALU work and registers in this loop
+  const int lane4 = (hi * 16 + col) * 4;
+  const int x16 = lane4 ^ 64, x32 = lane4 ^ 128;
+  const int arow = hi * (16 + 4) * 4;              // lane hi*16 + hi*4 (+ r)
+  const int asrc_a = (col + (((2 * hi) & 3) << 4)) * 4;
+  const int asrc_b = (col + (((2 * hi + 1) & 3) << 4)) * 4;
+  // ---- this page's V: in flight under the score MFMAs -----------------
+  {
+    // wave-uniform 64-bit base + 32-bit lane offset: one address VGPR
+    const char* vbase = reinterpret_cast<const char*>(
+        vc + (((long long)page * KVH + kvh) * D) * QSA_PAGE);
+#pragma unroll
+    for (int half = 0; half < 2; ++half)
+#pragma unroll
+      for (int dt = 0; dt < DTILES; ++dt)
+        vfr[half][dt] = *reinterpret_cast<const bf16x8_a*>(
+            vbase + (unsigned)(voff + (dt * 16 * QSA_PAGE + half * 32) * 2));
+  }
+  // keep the V loads ahead of the wait for K: left alone, the scheduler
+  // sinks them below the first score MFMAs, i.e. behind K's latency
+  __builtin_amdgcn_sched_barrier(0);
+  const int nvalid = min(seqlen - pi * QSA_PAGE, QSA_PAGE);
+
+  // ---- scores: 4 pos-tiles x KSTEPS MFMAs -----------------------------
+  f32x4_a sc[4];
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt) {
+    f32x4_a acc = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+      acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kfr[pt][ks], qf[ks],
+                                                    acc, 0, 0, 0);
+    sc[pt] = acc;
+  }
+
+  // ---- next page's K: in flight under softmax + PV --------------------
+  if (PREFETCH) {
+    page = page_n;
+    page_n = btab[min(pi + 2, p1 - 1)];
+    const char* kbase = reinterpret_cast<const char*>(
+        kc + ((((long long)page * KVH + kvh) * (D / 8)) * QSA_PAGE) * 8);
+#pragma unroll
+    for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+      for (int ks = 0; ks < KSTEPS; ++ks)
+        kfr[pt][ks] = *reinterpret_cast<const bf16x8_a*>(
+            kbase + (unsigned)(koff + (ks * 4 * QSA_PAGE + pt * 16) * 16));
+  }
+
+  // ---- online softmax (qsa_paged_attn_mfma's, verbatim) ---------------
+  float pagemax = -3.0e38f;
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int kpos = pt * 16 + hi * 4 + r;
+      float v = (kpos < nvalid) ? sc[pt][r] * scale : -3.0e38f;
+      sc[pt][r] = v;
+      pagemax = fmaxf(pagemax, v);
+    }
+  }
+  pagemax = fmaxf(pagemax, qsa_bperm_f(x16, pagemax));
+  pagemax = fmaxf(pagemax, qsa_bperm_f(x32, pagemax));
+  const float m_new = fmaxf(m, pagemax);
+  float alpha = __expf(m - m_new);
+  if (m <= -3.0e38f) alpha = 0.f;
+  m = m_new;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const float alpha_r = qsa_bperm_f(arow + r * 4, alpha);
+#pragma unroll
+    for (int dt = 0; dt < DTILES; ++dt) o_acc[dt][r] *= alpha_r;
+  }
+  unsigned int ppk[8];
+  float psum = 0.f;
+#pragma unroll
+  for (int pt = 0; pt < 4; ++pt) {
+    float p0f = 0.f, p1f = 0.f, p2f = 0.f, p3f = 0.f;
+    if (sc[pt][0] > -1.0e38f) p0f = __expf(sc[pt][0] - m_new);
+    if (sc[pt][1] > -1.0e38f) p1f = __expf(sc[pt][1] - m_new);
+    if (sc[pt][2] > -1.0e38f) p2f = __expf(sc[pt][2] - m_new);
+    if (sc[pt][3] > -1.0e38f) p3f = __expf(sc[pt][3] - m_new);
+    psum += p0f + p1f + p2f + p3f;
+    ppk[pt * 2] = f32x2_to_bf16x2(p0f, p1f);
+    ppk[pt * 2 + 1] = f32x2_to_bf16x2(p2f, p3f);
+  }
+  psum += qsa_bperm_f(x16, psum);
+  psum += qsa_bperm_f(x32, psum);
+  lsum = lsum * alpha + psum;
+
+  // ---- PV: two 32-pos halves (P repack as qsa_paged_attn_mfma) --------
+#pragma unroll
+  for (int half = 0; half < 2; ++half) {
+    const int tA = half * 2;
+    const int tB = half * 2 + 1;
+    const unsigned int a0A = qsa_bperm_u(asrc_a, ppk[tA * 2]);
+    const unsigned int a1A = qsa_bperm_u(asrc_a, ppk[tA * 2 + 1]);
+    const unsigned int b0A = qsa_bperm_u(asrc_b, ppk[tA * 2]);
+    const unsigned int b1A = qsa_bperm_u(asrc_b, ppk[tA * 2 + 1]);
+    const unsigned int a0B = qsa_bperm_u(asrc_a, ppk[tB * 2]);
+    const unsigned int a1B = qsa_bperm_u(asrc_a, ppk[tB * 2 + 1]);
+    const unsigned int b0B = qsa_bperm_u(asrc_b, ppk[tB * 2]);
+    const unsigned int b1B = qsa_bperm_u(asrc_b, ppk[tB * 2 + 1]);
+    const bool lo = hi < 2;
+    const u32x4_a pu = {lo ? a0A : a0B, lo ? a1A : a1B,
+                        lo ? b0A : b0B, lo ? b1A : b1B};
+    const bf16x8_a pa = __builtin_bit_cast(bf16x8_a, pu);
+#pragma unroll
+    for (int dt = 0; dt < DTILES; ++dt)
+      o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+          pa, vfr[half][dt], o_acc[dt], 0, 0, 0);
+  }
+}
+
+// ---------------------------------------------------------------------------
+// FUSED decode step: RoPE + KV append + pipelined flash-decode + split merge
+// in ONE launch (what LlamaModel.forward_decode runs).  Bit-identical to
+// qsa_rope_kv_append -> qsa_paged_attn_mfma -> qsa_attn_reduce: the same
+// wave/split/page decomposition, MFMA order, online softmax and P repack;
+// only WHEN loads are issued and WHERE the partials meet changes.
+//
+//   RoPE     q arrives un-rotated.  A lane's Q fragments hold
+//            k = ks*32 + hi*8 + e, whose rotation partner k +- D/2 is
+//            fragment ks ^ (KSTEPS/2) of the SAME lane: rotated in registers
+//            with qsa_rope_kv_append's expressions, never written back.
+//   append   the one wave whose split owns page (seq_len-1)/64 rotates the
+//            new k row, stores it and v into the cache, and makes the
+//            stores visible (workgroup fence) BEFORE it issues any K/V load
+//            of that page; no other wave of the grid reads that page.
+//   loop     a page's 16 K fragments load back to back into kfr[][], its 16
+//            V fragments into vfr[][] at the top of the iteration, and the
+//            NEXT page's K loads issue right after the score MFMAs, so
+//            softmax + PV run under 16 KiB of K in flight and the scores run
+//            under 16 KiB of V.  Block-table entries are scalar loads
+//            issued one page before the address that needs them, so no
+//            address waits on a table load and the vector-memory counter
+//            only ever counts K/V fragments.  Prefetch never goes through
+//            an entry past p1-1.
+//   merge    NS <= 4: all splits of (b, kvh) are waves of this workgroup.
+//            (m, l, o) meet in LDS and every thread evaluates
+//            qsa_attn_reduce's formula in its order; bf16 out is written
+//            directly.  NS > 4: fp32 partials + qsa_attn_reduce as before.
+// WPE = waves per SIMD the register budget is held to (1: <= 512 unified
+// registers, 2: <= 256).
+// ---------------------------------------------------------------------------
+template <int D, int WPE>
+__global__ void __launch_bounds__(256, WPE)
+qsa_paged_attn_mfma_fused(
+    const unsigned short* __restrict__ q,     // [B, QH, D] strided, UN-rotated
+    const unsigned short* __restrict__ knew,  // [B, KVH, D] strided
+    const unsigned short* __restrict__ vnew,  // [B, KVH, D] strided
+    unsigned short* kc,                       // [P, KVH, D/8, 64, 8]
+    unsigned short* vc,                       // [P, KVH, D, 64]
+    const float* __restrict__ cos_t, const float* __restrict__ sin_t,
+    const int* __restrict__ block_table,      // [B, max_pages]
+    const int* __restrict__ seq_lens,         // [B]
+    float* __restrict__ part_o,               // [B, QH, NS, D]   (NS > 4)
+    float* __restrict__ part_ml,              // [B, QH, NS, 2]   (NS > 4)
+    unsigned short* __restrict__ out,         // [B, QH, D]       (NS <= 4)
+    float scale, int B, int QH, int KVH, int max_pages, long long qstride,
+    long long kvstride, int NS) {
+  constexpr int KSTEPS = D / 32;
+  constexpr int DTILES = D / 16;
+  constexpr int HALF = D / 2;
+  constexpr int KH = KSTEPS / 2;      // fragment distance of a RoPE partner
+  constexpr int OP = D + 4;           // LDS pitch of one head's o row (floats)
+  // [4 splits][16 heads][OP] o, then [4][16][2] (m, l)
+  __shared__ float4 lds4[(4 * 16 * OP + 4 * 16 * 2) / 4];
+  float* lds_o = reinterpret_cast<float*>(lds4);
+  float* lds_ml = lds_o + 4 * 16 * OP;
+
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  const int nsb = (NS + 3) / 4;
+  const int bk = blockIdx.x / nsb;
+  const int split = (blockIdx.x % nsb) * 4 + wave;
+  const int b = bk / KVH;
+  const int kvh = bk % KVH;
+  const int R = QH / KVH;
+  const bool merge = NS <= 4;
+
+  const int seqlen = seq_lens[b];
+  const int npages = (seqlen + QSA_PAGE - 1) / QSA_PAGE;
+  const int chunk = (npages + NS - 1) / NS;
+  const int p0 = split * chunk;
+  const int p1 = min(npages, p0 + chunk);
+  const int col = lane & 15;
+  const int hi = lane >> 4;
+  const bool live = split < NS && seqlen > 0 && p0 < npages;
+
+  float m = -3.0e38f, lsum = 0.f;
+  f32x4_a o_acc[DTILES];
+#pragma unroll
+  for (int dt = 0; dt < DTILES; ++dt)
+    o_acc[dt] = (f32x4_a){0.f, 0.f, 0.f, 0.f};
+
+  if (live) {
+    const int* btab = block_table + (long long)b * max_pages;
+    const int pos = seqlen - 1;
+    const float* cosr = cos_t + (long long)pos * HALF;
+    const float* sinr = sin_t + (long long)pos * HALF;
+
+    // ---- append: only the split that owns the last page -----------------
+    if (p1 == npages) {
+      const int page = btab[npages - 1];
+      const int pin = pos % QSA_PAGE;
+      if (lane < D / 16) {
+        // 8 dims j*8.. and their +D/2 partners, as qsa_rope_kv_scatter
+        const int j = lane;
+        const unsigned short* base =
+            knew + (long long)b * kvstride + (long long)kvh * D + j * 8;
+        float c[8], s[8];
+        *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cosr + j * 8);
+        *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cosr + j * 8 + 4);
+        *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sinr + j * 8);
+        *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sinr + j * 8 + 4);
+        uint4 a4 = *reinterpret_cast<const uint4*>(base);
+        uint4 b4 = *reinterpret_cast<const uint4*>(base + HALF);
+        unsigned int* au = reinterpret_cast<unsigned int*>(&a4);
+        unsigned int* bu = reinterpret_cast<unsigned int*>(&b4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float2 x0 = bf16x2_to_f32x2(au[e]);
+          const float2 x1 = bf16x2_to_f32x2(bu[e]);
+          const float c0 = c[2 * e], c1 = c[2 * e + 1];
+          const float s0 = s[2 * e], s1 = s[2 * e + 1];
+          au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
+                  ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
+          bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
+                  ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
+        }
+        unsigned short* kdst = kc +
+            (((((long long)page * KVH + kvh) * (D / 8) + j) * QSA_PAGE) + pin) * 8;
+        *reinterpret_cast<uint4*>(kdst) = a4;
+        *reinterpret_cast<uint4*>(kdst + (long long)(HALF / 8) * QSA_PAGE * 8) = b4;
+      }
+      const unsigned short* vrow =
+          vnew + (long long)b * kvstride + (long long)kvh * D;
+      unsigned short* vdst =
+          vc + (((long long)page * KVH + kvh) * D) * QSA_PAGE + pin;
+#pragma unroll
+      for (int d = lane; d < D; d += QSA_WAVE)
+        vdst[(long long)d * QSA_PAGE] = vrow[d];
+      // the other lanes of this wave load these rows below
+      __threadfence_block();
+    }
+
+    // ---- Q B-fragments, rotated in registers ------------------------------
+    const int qh_l = kvh * R + min(col, R - 1);   // clamp: pad heads compute
+    const unsigned short* qrow = q + (long long)b * qstride + (long long)qh_l * D;
+    bf16x8_a qf[KSTEPS];
+#pragma unroll
+    for (int ks = 0; ks < KSTEPS; ++ks)
+      qf[ks] = *reinterpret_cast<const bf16x8_a*>(qrow + ks * 32 + hi * 8);
+#pragma unroll
+    for (int ks = 0; ks < KH; ++ks) {
+      float c[8], s[8];
+      const int o = ks * 32 + hi * 8;
+      *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cosr + o);
+      *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cosr + o + 4);
+      *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sinr + o);
+      *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sinr + o + 4);
+      u32x4_a au = __builtin_bit_cast(u32x4_a, qf[ks]);
+      u32x4_a bu = __builtin_bit_cast(u32x4_a, qf[ks + KH]);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float2 x0 = bf16x2_to_f32x2(au[e]);
+        const float2 x1 = bf16x2_to_f32x2(bu[e]);
+        const float c0 = c[2 * e], c1 = c[2 * e + 1];
+        const float s0 = s[2 * e], s1 = s[2 * e + 1];
+        au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
+                ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
+        bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
+                ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
+      }
+      qf[ks] = __builtin_bit_cast(bf16x8_a, au);
+      qf[ks + KH] = __builtin_bit_cast(bf16x8_a, bu);
+    }
+
+    // ---- block-table entries: wave-uniform scalar loads, read one page
+    // ahead of their use and never past entry p1-1 --------------------------
+    int page = btab[p0];
+    int page_n = btab[min(p0 + 1, p1 - 1)];
+
+    // lane's fragment offsets inside a (page, kv head) block, in bytes
+    const int koff = (hi * QSA_PAGE + col) * 16;      // + (ks*4*64 + pt*16)*16
+    const int voff = (col * QSA_PAGE + hi * 8) * 2;   // + (dt*16*64 + half*32)*2
+    bf16x8_a kfr[4][KSTEPS];
+    bf16x8_a vfr[2][DTILES];
+    {
+      const char* kbase = reinterpret_cast<const char*>(
+          kc + ((((long long)page * KVH + kvh) * (D / 8)) * QSA_PAGE) * 8);
+#pragma unroll
+      for (int pt = 0; pt < 4; ++pt)
+#pragma unroll
+        for (int ks = 0; ks < KSTEPS; ++ks)
+          kfr[pt][ks] = *reinterpret_cast<const bf16x8_a*>(
+              kbase + (unsigned)(koff + (ks * 4 * QSA_PAGE + pt * 16) * 16));
+    }
+
+    // all pages but the last prefetch their successor's K
+    for (int pi = p0; pi < p1 - 1; ++pi)
+      qsa_decode_page<D, true>(kc, vc, btab, pi, p1, seqlen, KVH, kvh, koff,
+                               voff, col, hi, scale, page, page_n, qf, kfr,
+                               vfr, o_acc, m, lsum);
+    qsa_decode_page<D, false>(kc, vc, btab, p1 - 1, p1, seqlen, KVH, kvh,
+                              koff, voff, col, hi, scale, page, page_n, qf,
+                              kfr, vfr, o_acc, m, lsum);
+  }
+
+  if (!merge) {
+    // ---- NS > 4: fp32 partials for qsa_attn_reduce -------------------------
+    if (split >= NS) return;
+    float* pml_base =
+        part_ml + (((long long)b * QH + kvh * R) * NS + split) * 2;
+    if (live) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int head = hi * 4 + r;
+        if (head < R) {
+          float* po = part_o +
+              (((long long)b * QH + kvh * R + head) * NS + split) * D;
+#pragma unroll
+          for (int dt = 0; dt < DTILES; ++dt)
+            po[dt * 16 + col] = o_acc[dt][r];
+        }
+      }
+    }
+    if (lane < R)
+      *reinterpret_cast<float2*>(pml_base + (long long)lane * NS * 2) =
+          make_float2(m, lsum);
+    return;
+  }
+
+  // ---- NS <= 4: the splits are this workgroup's waves; merge through LDS --
+  if (split < NS) {
+    if (live) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int head = hi * 4 + r;
+        if (head < R) {
+          float* po = lds_o + (wave * 16 + head) * OP;
+#pragma unroll
+          for (int dt = 0; dt < DTILES; ++dt)
+            po[dt * 16 + col] = o_acc[dt][r];
+        }
+      }
+    }
+    if (lane < R)
+      *reinterpret_cast<float2*>(lds_ml + (wave * 16 + lane) * 2) =
+          make_float2(m, lsum);
+  }
+  __syncthreads();
+  // qsa_attn_reduce's formula, in its order, per (head, d)
+  for (int idx = threadIdx.x; idx < R * D; idx += 256) {
+    const int head = idx / D;
+    const int d = idx % D;
+    float M = -3.0e38f;
+    for (int s = 0; s < NS; ++s)
+      if (lds_ml[(s * 16 + head) * 2 + 1] > 0.f)
+        M = fmaxf(M, lds_ml[(s * 16 + head) * 2]);
+    float L = 0.f, acc = 0.f;
+    for (int s = 0; s < NS; ++s) {
+      const float ls = lds_ml[(s * 16 + head) * 2 + 1];
+      if (ls <= 0.f) continue;
+      const float w = __expf(lds_ml[(s * 16 + head) * 2] - M);
+      L += w * ls;
+      acc += w * lds_o[(s * 16 + head) * OP + d];
+    }
+    const float v = (L > 0.f) ? acc / L : 0.f;
+    out[((long long)b * QH + kvh * R + head) * D + d] = f32_to_bf16(v);
+  }
+}
+
+// variant: waves per SIMD the kernel is compiled for (1 or 2)
+extern "C" void qsa_paged_attn_mfma_fused_launch(
+    const unsigned short* q, const unsigned short* knew,
+    const unsigned short* vnew, unsigned short* kc, unsigned short* vc,
+    const float* cos_t, const float* sin_t, const int* block_table,
+    const int* seq_lens, float* part_o, float* part_ml, unsigned short* out,
+    float scale, int B, int QH, int KVH, int max_pages, int D,
+    long long qstride, long long kvstride, int NS, int variant,
+    hipStream_t stream) {
+  const int nsb = (NS + 3) / 4;
+  dim3 grid(B * KVH * nsb);
+  dim3 block(256);
+#define QSA_FUSED_CASE(DD, WW)                                              \
+  if (D == DD && variant == WW) {                                           \
+    hipLaunchKernelGGL((qsa_paged_attn_mfma_fused<DD, WW>), grid, block, 0, \
+                       stream, q, knew, vnew, kc, vc, cos_t, sin_t,         \
+                       block_table, seq_lens, part_o, part_ml, out, scale,  \
+                       B, QH, KVH, max_pages, qstride, kvstride, NS);       \
+    if (NS > 4)                                                             \
+      hipLaunchKernelGGL((qsa_attn_reduce<DD>), dim3(B * QH), dim3(DD), 0,  \
+                         stream, part_o, part_ml, out, NS);                 \
+    return;                                                                 \
+  }
+  QSA_FUSED_CASE(128, 1) QSA_FUSED_CASE(128, 2)
+  QSA_FUSED_CASE(64, 1) QSA_FUSED_CASE(64, 2)
+#undef QSA_FUSED_CASE
 }
 
 // ---------------------------------------------------------------------------
