@@ -233,10 +233,15 @@ class LlamaModel:
         n, k = w.shape
         M = x.shape[0]
         if x.is_cuda and wf8 is not None:
-            if M <= 32:
+            # 33..64 rows only for the shape classes where the four-m-tile
+            # kernel beats rocBLAS (D.skinny_fp8_row_limit; measured at
+            # M = 64 on decode projections).  The limit is by row count,
+            # not by caller: eager decode and the last-position lm_head of
+            # a prefill batch with that many rows take the same route.
+            if M <= 32 or M <= D.skinny_fp8_row_limit(n, k):
                 return D.skinny_linear_fp8(x, wf8[0], wf8[1], n, k)
-            # 32 < M <= 256 (continuous-batching decode): the batched fp8
-            # kernel (ops/hip/gemm_fp8_batch.hip) is measured SLOWER than
+            # above that, up to 256 (continuous-batching decode): the batched
+            # fp8 kernel (ops/hip/gemm_fp8_batch.hip) is measured SLOWER than
             # rocBLAS bf16 at these M on MI355X — the problem is L2-/
             # compute-bound, not weight-stream-bound, so halved weight
             # bytes don't pay (profiles/fp8_decode_gemm.md).  Keep it

@@ -15,6 +15,11 @@ sequence alive between turns, the engine rolls the cache back to the shared
 prompt prefix and prefills only the delta (observation text) — turn N of an
 episode costs O(new tokens), not O(whole transcript).
 
+The decode step is hipGraph-captured at a ladder of row counts (16, 32, 64,
+max_batch) and each run replays the smallest rung that holds its live rows,
+so a nearly drained batch pays for its own rows, not for max_batch
+(QSA_DECODE_LADDER=0: one max_batch graph).
+
 Sampling: free text decodes greedily (deterministic); grammar decision
 tokens sample from the model's masked distribution under a fixed seed
 (models/grammar.py) — the whole benchmark stays reproducible.
@@ -60,11 +65,38 @@ class EngineStats:
     wall_s: float = 0.0
     prefill_s: float = 0.0
     decode_s: float = 0.0
+    # decode steps bucketed by live rows (len(batch) of the run), and graph
+    # replays bucketed by the ladder rung that ran them
+    decode_steps_by_live: dict = field(default_factory=dict)
+    decode_steps_by_rung: dict = field(default_factory=dict)
 
 
 import os as _os
 _TIMING = _os.environ.get("QSA_TIMING", "") == "1"
 _TUNABLE_DONE = False
+# QSA_DECODE_LADDER=0 (read once, here) restores the single max_batch decode
+# graph for A/B runs; tests flip the module attribute.
+DECODE_LADDER = _os.environ.get("QSA_DECODE_LADDER", "1") != "0"
+# row counts of the decode-graph ladder below max_batch, which is always a
+# rung.  Each is faster than the next larger rung by far more than the
+# run-to-run spread on MI355X; 128 was not (7.27 against 7.16 ms at
+# max_batch 192) and is left out (profiles/README.md, "Decode ladder").
+LADDER_CANDIDATES = (16, 32, 64)
+
+
+def ladder_rungs(max_batch: int, ladder: bool = True) -> tuple:
+    """Row counts the decode graph is captured at, ascending."""
+    if not ladder:
+        return (max_batch,)
+    return tuple(c for c in LADDER_CANDIDATES if c < max_batch) + (max_batch,)
+
+
+def pick_rung(rungs: tuple, n: int) -> int:
+    """Smallest rung that holds n live rows (rungs ascending)."""
+    for r in rungs:
+        if r >= n:
+            return r
+    raise ValueError(f"{n} live rows exceed the largest rung {rungs[-1]}")
 
 
 def _enable_tunableop() -> None:
@@ -140,15 +172,19 @@ class Engine:
         # nothing (every decoded token reads back as 0).
         self.use_graph = torch.cuda.is_available() and \
             torch.device(model.device).type == "cuda"
-        self._graph = None
+        self._graph = None       # the max_batch rung's graph
+        self._graphs: dict = {}  # rung (rows) -> captured graph
+        self._rungs: tuple = ()
         self._graph_failed = False
         self._gbuf: dict = {}
         # free-text sampling mask: tokens outside [lo, hi) (plus EOS) are
         # never emitted — keeps random-init decode inside the tokenizer's
         # trained vocab so outputs are real text (models/grammar.py)
         self._vocab_bias: torch.Tensor | None = None
+        self._valid_vocab = None
         if valid_vocab is not None:
             lo, hi = valid_vocab
+            self._valid_vocab = (int(lo), int(hi))
             bias = torch.full((model.cfg.vocab_size,), float("-inf"),
                               device=model.device, dtype=torch.float32)
             bias[lo:hi] = 0.0
@@ -214,10 +250,22 @@ class Engine:
             self._graph_failed = True
             self.use_graph = False
             self._graph = None
+            self._graphs = {}
             torch.cuda.synchronize()
             return False
 
+    def _fused_sampler(self, logits: torch.Tensor) -> bool:
+        """The one-launch greedy sampler (ops/hip/elementwise.hip) applies
+        to greedy decoding of GPU bf16 logits under a vocab window."""
+        return self.temperature <= 0.0 and self._valid_vocab is not None \
+            and logits.is_cuda and logits.dtype == torch.bfloat16
+
     def _capture_graph(self) -> None:
+        """Capture the decode step once per ladder rung.  Every rung works
+        on the leading rows of the same max_batch buffers and all rungs
+        share one memory pool (they never replay concurrently), so a small
+        rung costs its kernels, not its own activations."""
+        from ..ops import dispatch as D
         dev = self.model.device
         B = self.max_batch
         cap = (self.max_seq_len + 63) // 64
@@ -234,36 +282,57 @@ class Engine:
                                   device=dev),
             "script_mask": torch.zeros(B, self.MAX_RUN, dtype=torch.bool,
                                        device=dev),
+            # scratch of the fused sampler kernel
+            "ticket": torch.zeros(1, dtype=torch.int32, device=dev),
         }
+        eos = -1 if self.eos_id is None else int(self.eos_id)
 
-        def body():
-            # self-feeding decode step: advance seq_lens in-graph, append the
-            # step's k/v at seq_lens-1, attend, sample, record, feed back.
-            gb["seq_lens"].add_(gb["active"])
-            positions = (gb["seq_lens"] - 1).clamp(min=0).int()
+        def body(b: int):
+            # self-feeding decode step on rows [0, b): advance seq_lens
+            # in-graph, append the step's k/v at seq_lens-1, attend, sample,
+            # record, feed back.  forward_decode derives positions from
+            # seq_lens itself; its `positions` argument is unused.
+            tokens, seq_lens = gb["tokens"][:b], gb["seq_lens"][:b]
+            seq_lens.add_(gb["active"][:b])
             logits = self.model.forward_decode(
-                gb["tokens"], self.kv, gb["block_table"], gb["seq_lens"],
-                positions)
+                tokens, self.kv, gb["block_table"][:b], seq_lens, None)
+            if self._fused_sampler(logits):
+                lo, hi = self._valid_vocab
+                D.greedy_sample_step(
+                    logits, lo, hi, eos, gb["script"][:b],
+                    gb["script_mask"][:b], gb["ctr"], gb["hist"][:, :b],
+                    tokens, gb["ticket"])
+                return
             nxt = self._sample(logits)
             # grammar-forced tokens override the free sample in-graph
             j = gb["ctr"].clamp(max=self.MAX_RUN - 1)
-            forced = gb["script"].index_select(1, j).squeeze(1)
-            fmask = gb["script_mask"].index_select(1, j).squeeze(1)
+            forced = gb["script"][:b].index_select(1, j).squeeze(1)
+            fmask = gb["script_mask"][:b].index_select(1, j).squeeze(1)
             nxt = torch.where(fmask, forced, nxt)
-            gb["hist"].index_copy_(0, gb["ctr"], nxt.unsqueeze(0))
+            gb["hist"][:, :b].index_copy_(0, gb["ctr"], nxt.unsqueeze(0))
             gb["ctr"].add_(1)
-            gb["tokens"].copy_(nxt)
+            tokens.copy_(nxt)
 
-        # warm up the exact captured ops (allocator + rocBLAS algo selection)
-        for _ in range(2):
-            body()
-        gb["ctr"].zero_()
-        gb["seq_lens"].zero_()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            body()
-        self._graph = g
+        rungs = ladder_rungs(B, DECODE_LADDER)
+        graphs: dict = {}
+        pool = None
+        for b in reversed(rungs):     # largest first: it sizes the pool
+            # warm up the exact captured ops (allocator + rocBLAS algo
+            # selection)
+            for _ in range(2):
+                body(b)
+            gb["ctr"].zero_()
+            gb["seq_lens"].zero_()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, pool=pool):
+                body(b)
+            if pool is None:
+                pool = g.pool()
+            graphs[b] = g
+        self._graphs = graphs
+        self._rungs = rungs
+        self._graph = graphs[B]
         self._gbuf = gb
 
     def _decode_run_eager(self, batch: list[Sequence], run: int) -> None:
@@ -300,6 +369,8 @@ class Engine:
             self._maybe_finish(s)
         self.stats.decode_tokens += len(batch)
         self.stats.decode_steps += 1
+        by_live = self.stats.decode_steps_by_live
+        by_live[len(batch)] = by_live.get(len(batch), 0) + 1
 
     def _decode_run_graph(self, batch: list[Sequence], run: int) -> None:
         """Run `run` decode steps for `batch` with zero host round trips:
@@ -361,8 +432,12 @@ class Engine:
         if _TIMING:
             torch.cuda.synchronize()
             self._t_graph0 = time.perf_counter()
+        # the rung depends on len(batch) alone, so the schedule and the
+        # results stay a deterministic function of the inputs
+        self._rung = pick_rung(self._rungs, n)
+        g = self._graphs[self._rung]
         for _ in range(run):
-            self._graph.replay()
+            g.replay()
 
     def _graph_run_end(self, batch: list[Sequence], run: int) -> None:
         gb = self._gbuf
@@ -381,6 +456,10 @@ class Engine:
             self._maybe_finish(s)
         self.stats.decode_tokens += n * run
         self.stats.decode_steps += run
+        by_live = self.stats.decode_steps_by_live
+        by_live[n] = by_live.get(n, 0) + run
+        by_rung = self.stats.decode_steps_by_rung
+        by_rung[self._rung] = by_rung.get(self._rung, 0) + run
 
     # ------------------------------------------------------------------
     def submit(self, prompt_tokens: list[int], max_new_tokens: int,

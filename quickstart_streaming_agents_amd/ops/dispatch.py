@@ -256,11 +256,84 @@ def gemm_fp8_batch(x: torch.Tensor, qf: torch.Tensor,
 
 def skinny_linear_fp8(x: torch.Tensor, qf: torch.Tensor,
                       scale: torch.Tensor, n: int, k: int) -> torch.Tensor:
-    """x[M,K] bf16 @ dequant(Q)^T via the fp8 weight-streaming kernel."""
+    """x[M,K] bf16 @ dequant(Q)^T via the fp8 weight-streaming kernel
+    (M <= 64)."""
     if x.is_cuda:
         return ext().skinny_gemm_fp8(x, qf, scale, n, k)
     w = unpack_weight_fp8(qf, scale, n, k)
     return (x.float() @ w.T).to(x.dtype)
+
+
+# Shape classes that beat rocBLAS bf16 at 33..64 rows on MI355X, measured at
+# M = 64 (profiles/fp8_decode_gemm.md): only wo-like weights (small N,
+# K < 8192).  Every other class keeps the 32-row limit.
+SKINNY_FP8_WIDE_CLASSES: frozenset = frozenset({"wo"})
+
+
+def skinny_fp8_class(n: int, k: int) -> str:
+    """The fp8 skinny launcher's shape class for an [n, k] weight
+    (ops/hip/skinny_gemm_fp8.hip), its last class split by K: the launch
+    is the same for wo and wdown, the comparison with rocBLAS is not.
+    Mirrors qsa_skinny_gemm_fp8_launch_mt: change the two together."""
+    if n % 128 == 0 and n >= 65536:
+        return "lm_head"
+    if n % 64 == 0 and n >= 16384:
+        return "wgu"
+    if n % 32 == 0 and n >= 6144 and k < 8192:
+        return "qkv"
+    return "wo" if k < 8192 else "wdown"
+
+
+def skinny_fp8_row_limit(n: int, k: int) -> int:
+    """Largest M routed to the fp8 skinny kernel for an [n, k] weight."""
+    return 64 if skinny_fp8_class(n, k) in SKINNY_FP8_WIDE_CLASSES else 32
+
+
+# ---- fused greedy sampling step ------------------------------------------
+
+def greedy_sample_step(logits: torch.Tensor, lo: int, hi: int, eos: int,
+                       script: torch.Tensor, script_mask: torch.Tensor,
+                       ctr: torch.Tensor, hist: torch.Tensor,
+                       tokens: torch.Tensor,
+                       ticket: torch.Tensor | None = None) -> None:
+    """One decode step's greedy sampling and bookkeeping, in place.
+
+    tok[b] = lowest-index argmax of logits[b] over [lo, hi) U {eos}
+    (eos < 0: no eos), overridden by script[b, min(ctr, max_run - 1)]
+    where script_mask is set; then hist[ctr, b] = tok[b],
+    tokens[b] = tok[b], ctr += 1.  Rows beyond logits.shape[0] of script /
+    hist / tokens are left alone.  Equals argmax(logits.float() + bias)
+    with bias 0 on the set and -inf elsewhere, on NaN-free logits.
+    ticket: i32 [1] zero-initialised scratch of the GPU kernel."""
+    if logits.is_cuda:
+        ext().greedy_sample_step(logits, lo, hi, eos, script, script_mask,
+                                 ctr, hist, tokens, ticket)
+        return
+    B = logits.shape[0]
+    if B == 0:
+        return
+    win = logits[:, lo:hi].float()
+    if hi > lo:
+        bv, bi = win.max(dim=1)
+        # lowest index among ties (max's index choice is unspecified)
+        bi = (win == bv[:, None]).int().argmax(dim=1) + lo
+    else:
+        bv = torch.full((B,), float("-inf"))
+        bi = torch.zeros(B, dtype=torch.int64)
+    if eos >= 0 and not lo <= eos < hi:
+        ev = logits[:, eos].float()
+        take = (ev > bv) | ((ev == bv) & (eos < bi))
+        bi = torch.where(take, torch.full_like(bi, eos), bi)
+        bv = torch.where(take, ev, bv)
+    # an all -inf candidate set gives index 0, as torch.argmax does
+    bi = torch.where(bv == float("-inf"), torch.zeros_like(bi), bi)
+    c = int(ctr[0])
+    j = min(max(c, 0), script.shape[1] - 1)
+    tok = torch.where(script_mask[:B, j], script[:B, j], bi)
+    if 0 <= c < hist.shape[0]:
+        hist[c, :B] = tok
+    tokens[:B] = tok
+    ctr.add_(1)
 
 
 # ---- retrieval / streaming ------------------------------------------------

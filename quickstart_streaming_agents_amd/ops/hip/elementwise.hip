@@ -360,3 +360,103 @@ extern "C" void qsa_softmax_rows_bf16_launch(unsigned short* scores,
   hipLaunchKernelGGL(qsa_softmax_rows_bf16_kernel, dim3((unsigned)rows),
                      dim3(256), 0, stream, scores, cols, scale, row_limits);
 }
+
+// ---------------------------------------------------------------------------
+// Fused greedy sampling step of the captured decode graph (models/serve.py):
+// one workgroup per row replaces the bf16->f32 copy of [B, V], the vocab-bias
+// add, the argmax, the script gather + where, the history write and the
+// counter / token copies.
+//   tok  = argmax of logits[row, i] over i in [lo, hi) U {eos}, lowest index
+//          on ties (what torch.argmax gives on logits.float() + bias with
+//          bias 0 on that set and -inf elsewhere; bf16 -> f32 is exact)
+//   tok  = script[row, min(ctr, max_run-1)] where script_mask is set there
+//   hist[ctr, row] = tok; tokens[row] = tok; ctr += 1 (once per launch)
+// If every candidate is -inf the result is index 0, as torch.argmax of an
+// all -inf row.  NaN: a NaN logit never compares greater, so it is never
+// selected and the maximum of the other candidates wins, whereas
+// torch.argmax returns the first NaN's index; equivalence is claimed for
+// NaN-free logits only.
+// ctr is read by every workgroup and advanced by the last one to finish
+// (ticket counter, reset for the next launch), so no workgroup can observe
+// the advanced value.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void qsa_argmax_take(float& bv, int& bi, float v,
+                                                int i) {
+  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+}
+
+__global__ void __launch_bounds__(256)
+qsa_greedy_sample_kernel(const unsigned short* __restrict__ logits,  // [B,V]
+                         long long V, int lo, int hi, int eos,
+                         const long long* __restrict__ script,   // [B,max_run]
+                         const unsigned char* __restrict__ script_mask,
+                         int max_run,
+                         long long* __restrict__ ctr,            // [1]
+                         long long* __restrict__ hist,  // [hist_rows, stride]
+                         long long hist_stride, int hist_rows,
+                         long long* __restrict__ tokens,         // [B]
+                         unsigned int* __restrict__ ticket) {    // [1], 0
+  const int row = blockIdx.x;
+  const unsigned short* r = logits + (long long)row * V;
+  const float ninf = -__builtin_inff();
+  float bv = ninf;
+  int bi = 0;
+
+  // scalar head up to a 16-byte boundary, uint4 body, scalar tail
+  const int mis = (int)((reinterpret_cast<unsigned long long>(r + lo) >> 1) & 7);
+  const int body0 = min(hi, lo + ((8 - mis) & 7));
+  const int body1 = body0 + ((hi - body0) & ~7);
+  for (int i = lo + threadIdx.x; i < body0; i += blockDim.x)
+    qsa_argmax_take(bv, bi, bf16_to_f32(r[i]), i);
+  for (int i = body0 + threadIdx.x * 8; i < body1; i += blockDim.x * 8) {
+    const uint4 v4 = *reinterpret_cast<const uint4*>(r + i);
+    const unsigned int vv[4] = {v4.x, v4.y, v4.z, v4.w};
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float2 f = bf16x2_to_f32x2(vv[j]);
+      qsa_argmax_take(bv, bi, f.x, i + 2 * j);
+      qsa_argmax_take(bv, bi, f.y, i + 2 * j + 1);
+    }
+  }
+  for (int i = body1 + threadIdx.x; i < hi; i += blockDim.x)
+    qsa_argmax_take(bv, bi, bf16_to_f32(r[i]), i);
+  if (threadIdx.x == 0 && eos >= 0 && (eos < lo || eos >= hi))
+    qsa_argmax_take(bv, bi, bf16_to_f32(r[eos]), eos);
+
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    const float ov = __shfl_xor(bv, off, QSA_WAVE);
+    const int oi = __shfl_xor(bi, off, QSA_WAVE);
+    qsa_argmax_take(bv, bi, ov, oi);
+  }
+  __shared__ float sv[4];
+  __shared__ int si[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { sv[wave] = bv; si[wave] = bi; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < 4; ++w) qsa_argmax_take(bv, bi, sv[w], si[w]);
+    const long long c = ctr[0];
+    const long long j = c < (long long)max_run - 1 ? (c < 0 ? 0 : c)
+                                                   : (long long)max_run - 1;
+    const long long so = (long long)row * max_run + j;
+    const long long tok = script_mask[so] ? script[so] : (long long)bi;
+    if (c >= 0 && c < hist_rows) hist[c * hist_stride + row] = tok;
+    tokens[row] = tok;
+    __threadfence();
+    if (atomicAdd(ticket, 1u) == gridDim.x - 1) {
+      ctr[0] = c + 1;
+      *ticket = 0u;
+    }
+  }
+}
+
+extern "C" void qsa_greedy_sample_launch(
+    const unsigned short* logits, int B, long long V, int lo, int hi, int eos,
+    const long long* script, const unsigned char* script_mask, int max_run,
+    long long* ctr, long long* hist, long long hist_stride, int hist_rows,
+    long long* tokens, unsigned int* ticket, hipStream_t stream) {
+  hipLaunchKernelGGL(qsa_greedy_sample_kernel, dim3(B), dim3(256), 0, stream,
+                     logits, V, lo, hi, eos, script, script_mask, max_run,
+                     ctr, hist, hist_stride, hist_rows, tokens, ticket);
+}

@@ -96,6 +96,14 @@ extern "C" void qsa_skinny_gemm_fp8_probe_launch(
     const unsigned short*, const unsigned char*, const float*,
     unsigned short*, int, int, long long, long long, int, int, int,
     hipStream_t);
+extern "C" int qsa_skinny_gemm_fp8_probe_mt_launch(
+    const unsigned short*, const unsigned char*, const float*,
+    unsigned short*, int, int, long long, long long, int, int, int,
+    hipStream_t);
+extern "C" void qsa_greedy_sample_launch(
+    const unsigned short*, int, long long, int, int, int, const long long*,
+    const unsigned char*, int, long long*, long long*, long long, int,
+    long long*, unsigned int*, hipStream_t);
 extern "C" void qsa_gemm_fp8_batch_launch(const unsigned short*,
                                           const unsigned char*,
                                           const float*, unsigned short*,
@@ -605,7 +613,7 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor a, torch::Tensor qf,
               "scale must be f32 [N] on device");
   TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
   const int M = a.size(0);
-  TORCH_CHECK(M >= 1 && M <= 32, "skinny_gemm_fp8: M in [1,32]");
+  TORCH_CHECK(M >= 1 && M <= 64, "skinny_gemm_fp8: M in [1,64]");
   TORCH_CHECK(a.size(1) == K, "K mismatch");
   TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "K%256==0, N%16==0");
   TORCH_CHECK(qf.numel() == (long long)N * K, "qf size");
@@ -627,6 +635,68 @@ torch::Tensor skinny_gemm_fp8_probe(torch::Tensor a, torch::Tensor qf,
                                    (int)N, K, a.stride(0), (int)waves,
                                    (int)tiles, (int)nt, cur_stream());
   return out;
+}
+
+torch::Tensor skinny_gemm_fp8_probe_mt(torch::Tensor a, torch::Tensor qf,
+                                       torch::Tensor scale, long N, long K,
+                                       long waves, long tiles, long mt) {
+  CHK_DEV(a); CHK_BF16(a); CHK_CONT(qf); CHK_DEV(qf); CHK_DEV(scale);
+  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
+  const int M = a.size(0);
+  TORCH_CHECK(mt >= 1 && M >= 1 && M <= 16 * mt, "M in [1, 16*mt]");
+  TORCH_CHECK(a.size(1) == K && K % 256 == 0 && tiles >= 1 &&
+                  N % (16 * tiles) == 0,
+              "K%256==0, N%(16*tiles)==0");
+  TORCH_CHECK(qf.numel() == (long long)N * K && scale.numel() == N,
+              "qf / scale size");
+  auto out = torch::empty({M, (long long)N}, a.options());
+  const int ok = qsa_skinny_gemm_fp8_probe_mt_launch(
+      u16(a), qf.data_ptr<unsigned char>(), scale.data_ptr<float>(),
+      u16m(out), M, (int)N, K, a.stride(0), (int)waves, (int)tiles, (int)mt,
+      cur_stream());
+  TORCH_CHECK(ok, "skinny_gemm_fp8_probe_mt: variant not instantiated");
+  return out;
+}
+
+void greedy_sample_step(torch::Tensor logits, long lo, long hi, long eos,
+                        torch::Tensor script, torch::Tensor script_mask,
+                        torch::Tensor ctr, torch::Tensor hist,
+                        torch::Tensor tokens, torch::Tensor ticket) {
+  // One decode step's greedy sampling + bookkeeping in one launch
+  // (elementwise.hip): tokens/hist/ctr are updated in place.
+  CHK_DEV(logits); CHK_CONT(logits); CHK_BF16(logits);
+  CHK_DEV(script); CHK_CONT(script); CHK_DEV(script_mask);
+  CHK_CONT(script_mask); CHK_DEV(ctr); CHK_DEV(hist); CHK_DEV(tokens);
+  CHK_CONT(tokens); CHK_DEV(ticket);
+  TORCH_CHECK(logits.dim() == 2, "logits [B, V]");
+  const long long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= V, "0 <= lo <= hi <= V");
+  TORCH_CHECK(eos < V, "eos < V");
+  TORCH_CHECK(script.scalar_type() == at::kLong && script.dim() == 2 &&
+                  script.size(0) >= B, "script i64 [>=B, max_run]");
+  TORCH_CHECK(script_mask.scalar_type() == at::kBool &&
+                  script_mask.sizes() == script.sizes(),
+              "script_mask bool, same shape as script");
+  TORCH_CHECK(script.size(1) >= 1, "max_run >= 1");
+  TORCH_CHECK(ctr.scalar_type() == at::kLong && ctr.numel() == 1, "ctr i64 [1]");
+  TORCH_CHECK(hist.scalar_type() == at::kLong && hist.dim() == 2 &&
+                  hist.size(1) >= B && hist.stride(1) == 1,
+              "hist i64 [rows, >=B], unit column stride");
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.numel() >= B,
+              "tokens i64 [>=B]");
+  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() == 1,
+              "ticket i32 [1]");
+  if (B == 0) return;
+  qsa_greedy_sample_launch(
+      u16(logits), (int)B, V, (int)lo, (int)hi, eos < 0 ? -1 : (int)eos,
+      reinterpret_cast<const long long*>(script.data_ptr<int64_t>()),
+      reinterpret_cast<const unsigned char*>(script_mask.data_ptr<bool>()),
+      (int)script.size(1),
+      reinterpret_cast<long long*>(ctr.data_ptr<int64_t>()),
+      reinterpret_cast<long long*>(hist.data_ptr<int64_t>()), hist.stride(0),
+      (int)hist.size(0),
+      reinterpret_cast<long long*>(tokens.data_ptr<int64_t>()),
+      reinterpret_cast<unsigned int*>(ticket.data_ptr<int>()), cur_stream());
 }
 
 std::vector<torch::Tensor> topk_cosine(torch::Tensor queries,
@@ -728,6 +798,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "batched-M (<=256) fp8 weight-stream GEMM with optional split-K");
   m.def("skinny_gemm_fp8_probe", &skinny_gemm_fp8_probe,
         "fp8 ablation probe: waves/tiles/nt sweep");
+  m.def("skinny_gemm_fp8_probe_mt", &skinny_gemm_fp8_probe_mt,
+        "fp8 skinny GEMM with explicit (waves, tiles, m-tiles) for sweeps");
+  m.def("greedy_sample_step", &greedy_sample_step,
+        "fused greedy sampling step: windowed argmax, script override, "
+        "history/token/counter update (in place)");
   m.def("topk_cosine", &topk_cosine, "exact cosine top-k over the HBM index");
   m.def("hash_build", &hash_build,
         "build latest-per-key hash table from (keys, event ts)");

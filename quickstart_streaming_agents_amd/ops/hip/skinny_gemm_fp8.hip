@@ -1,5 +1,5 @@
 // FP8 (OCP e4m3) weight-streaming decode GEMM for CDNA4 (gfx950):
-// C[M,N] = A[M,K] @ (s[N] * Q[N,K])^T, M <= 32, A bf16, Q fp8, C bf16.
+// C[M,N] = A[M,K] @ (s[N] * Q[N,K])^T, M <= 64, A bf16, Q fp8, C bf16.
 // Serves the K4 agent-LLM decode projections.
 //
 // The bf16 skinny kernel (skinny_gemm.hip) is HBM-bound on the WEIGHT
@@ -58,7 +58,17 @@ __device__ __forceinline__ bf16x8 fp8x8_to_bf16x8(unsigned int a,
 // per k-step and reused across all TILES MFMA streams.  TILES=4 for the
 // big-N projections (wgu/lm_head), 1 for the small ones (grid must still
 // exceed 256 CUs).
-template <int WAVES, int TILES, bool NT>
+//
+// MT 16-row m-tiles per launch (2 or 4 -> M <= 32, 64; MT = 1 measured no
+// faster than 2 at M <= 16 on any shape and is not instantiated): only the A
+// fragments and the accumulators multiply; the weight stream, its layout
+// and the dequantisation are shared by all m-tiles.  One output element
+// accumulates over K in an order fixed by WAVES alone (chunks wave,
+// wave + WAVES, ... in sequence, then the waves in index order), and an
+// MFMA output row depends on its own A row only — so for a given WAVES a
+// row's output bits do not depend on MT, TILES or the other rows.  The
+// launcher keeps WAVES per shape class the same for every MT.
+template <int WAVES, int TILES, bool NT, int MT = 2>
 __global__ void __launch_bounds__(WAVES * 64)
 qsa_skinny_gemm_fp8_t(const unsigned short* __restrict__ A,  // [M,K] bf16
                       const u32x4* __restrict__ Qf,   // packed fp8 stream
@@ -70,20 +80,20 @@ qsa_skinny_gemm_fp8_t(const unsigned short* __restrict__ A,  // [M,K] bf16
   const int lane = threadIdx.x & 63;
   const long long kchunks = K / QSA_KCH8;  // K % 256 == 0
 
-  f32x4 acc0[TILES], acc1[TILES];
+  f32x4 acc[MT][TILES];
 #pragma unroll
-  for (int t = 0; t < TILES; ++t) {
-    acc0[t] = {0.f, 0.f, 0.f, 0.f};
-    acc1[t] = {0.f, 0.f, 0.f, 0.f};
+  for (int m = 0; m < MT; ++m) {
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) acc[m][t] = {0.f, 0.f, 0.f, 0.f};
   }
 
   // A rows clamp out-of-batch to M-1 (store is guarded; see bf16 kernel)
   const int arow = lane & 15;
   const int akoff = (lane >> 4) * 8;
-  const int r0 = min(arow, M - 1);
-  const int r1 = min(16 + arow, M - 1);
-  const unsigned short* a0base = A + (long long)r0 * lda + akoff;
-  const unsigned short* a1base = A + (long long)r1 * lda + akoff;
+  const unsigned short* abase[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+    abase[m] = A + (long long)min(16 * m + arow, M - 1) * lda + akoff;
 
   // Q stream: 1024-B block per (nt, kb=64k); this lane's 16 B at byte
   // (lane&15)*64 + (lane>>4)*16 inside the block (uint4 units below).
@@ -109,35 +119,37 @@ qsa_skinny_gemm_fp8_t(const unsigned short* __restrict__ A,  // [M,K] bf16
         }
       }
       const long long ak = k0 + s * 64;
-      const bf16x8 a00 = *reinterpret_cast<const bf16x8*>(a0base + ak);
-      const bf16x8 a10 = *reinterpret_cast<const bf16x8*>(a1base + ak);
-      const bf16x8 a01 = *reinterpret_cast<const bf16x8*>(a0base + ak + 32);
-      const bf16x8 a11 = *reinterpret_cast<const bf16x8*>(a1base + ak + 32);
+      bf16x8 a0[MT], a1[MT];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        a0[m] = *reinterpret_cast<const bf16x8*>(abase[m] + ak);
+        a1[m] = *reinterpret_cast<const bf16x8*>(abase[m] + ak + 32);
+      }
 #pragma unroll
       for (int t = 0; t < TILES; ++t) {
         const bf16x8 w0 = fp8x8_to_bf16x8(q[t].x, q[t].y);   // k .. +32
         const bf16x8 w1 = fp8x8_to_bf16x8(q[t].z, q[t].w);   // +32 .. +64
-        acc0[t] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a00, w0, acc0[t], 0, 0, 0);
-        acc1[t] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a10, w0, acc1[t], 0, 0, 0);
-        acc0[t] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a01, w1, acc0[t], 0, 0, 0);
-        acc1[t] =
-            __builtin_amdgcn_mfma_f32_16x16x32_bf16(a11, w1, acc1[t], 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+          acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a0[m], w0, acc[m][t], 0, 0, 0);
+#pragma unroll
+        for (int m = 0; m < MT; ++m)
+          acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+              a1[m], w1, acc[m][t], 0, 0, 0);
       }
     }
   }
 
   // ---- cross-wave K-reduction in LDS + per-channel scale ---------------
-  __shared__ float red[WAVES][64][8];
+  __shared__ float red[WAVES][64][4 * MT];
 #pragma unroll
   for (int t = 0; t < TILES; ++t) {
     if (t > 0) __syncthreads();   // reuse the LDS slab per tile
 #pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      red[wave][lane][r] = acc0[t][r];
-      red[wave][lane][4 + r] = acc1[t][r];
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) red[wave][lane][4 * m + r] = acc[m][t][r];
     }
     __syncthreads();
     if (wave == 0) {
@@ -145,19 +157,48 @@ qsa_skinny_gemm_fp8_t(const unsigned short* __restrict__ A,  // [M,K] bf16
       const int mrow = (lane >> 4) * 4;
       const float s = scale[ncol];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        float v0 = 0.f, v1 = 0.f;
+      for (int m = 0; m < MT; ++m) {
 #pragma unroll
-        for (int wv = 0; wv < WAVES; ++wv) {
-          v0 += red[wv][lane][r];
-          v1 += red[wv][lane][4 + r];
+        for (int r = 0; r < 4; ++r) {
+          float v = 0.f;
+#pragma unroll
+          for (int wv = 0; wv < WAVES; ++wv) v += red[wv][lane][4 * m + r];
+          const int mo = 16 * m + mrow + r;
+          if (mo < M) Cbf[(long long)mo * N + ncol] = f32_to_bf16(v * s);
         }
-        const int m0 = mrow + r;
-        if (m0 < M) Cbf[(long long)m0 * N + ncol] = f32_to_bf16(v0 * s);
-        if (16 + m0 < M)
-          Cbf[(long long)(16 + m0) * N + ncol] = f32_to_bf16(v1 * s);
       }
     }
+  }
+}
+
+// Per-shape winners from the measured sweep on MI355X
+// (profiles/fp8_decode_gemm.md): huge N wants more tiles + fewer
+// waves (lm_head w2t8 = 4.6 TB/s fp8 bytes), mid N wants t4, qkv-size
+// t2, small/deep-K t1.  WAVES is a function of the shape class only (see
+// the row-invariance note on the kernel); TILES may differ per MT.
+// ops/dispatch.py skinny_fp8_class() repeats these class conditions to
+// decide the 33..64-row routing: change the two together.
+template <int MT>
+static void qsa_skinny_gemm_fp8_launch_mt(
+    const unsigned short* A, const u32x4* Q, const float* scale,
+    unsigned short* Cbf, int M, int N, long long K, long long lda,
+    hipStream_t stream) {
+  if (N % 128 == 0 && N >= 65536) {          // lm_head class
+    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<2, 8, false, MT>),
+                       dim3(N / 128), dim3(128), 0, stream, A, Q, scale,
+                       Cbf, M, N, K, lda);
+  } else if (N % 64 == 0 && N >= 16384) {    // wgu class
+    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<8, 4, false, MT>),
+                       dim3(N / 64), dim3(512), 0, stream, A, Q, scale, Cbf,
+                       M, N, K, lda);
+  } else if (N % 32 == 0 && N >= 6144 && K < 8192) {   // qkv class
+    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<8, 2, false, MT>),
+                       dim3(N / 32), dim3(512), 0, stream, A, Q, scale, Cbf,
+                       M, N, K, lda);
+  } else {                                   // wo / wdown class
+    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<8, 1, false, MT>),
+                       dim3(N / 16), dim3(512), 0, stream, A, Q, scale, Cbf,
+                       M, N, K, lda);
   }
 }
 
@@ -165,28 +206,11 @@ extern "C" void qsa_skinny_gemm_fp8_launch(
     const unsigned short* A, const unsigned char* Qf, const float* scale,
     unsigned short* Cbf, int M, int N, long long K, long long lda,
     hipStream_t stream) {
-  // Per-shape winners from the measured sweep on MI355X
-  // (profiles/fp8_decode_gemm.md): huge N wants more tiles + fewer
-  // waves (lm_head w2t8 = 4.6 TB/s fp8 bytes), mid N wants t4, qkv-size
-  // t2, small/deep-K t1.
   const u32x4* Q = reinterpret_cast<const u32x4*>(Qf);
-  if (N % 128 == 0 && N >= 65536) {          // lm_head class
-    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<2, 8, false>), dim3(N / 128),
-                       dim3(128), 0, stream, A, Q, scale, Cbf, M, N, K,
-                       lda);
-  } else if (N % 64 == 0 && N >= 16384) {    // wgu class
-    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<8, 4, false>), dim3(N / 64),
-                       dim3(512), 0, stream, A, Q, scale, Cbf, M, N, K,
-                       lda);
-  } else if (N % 32 == 0 && N >= 6144 && K < 8192) {   // qkv class
-    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<8, 2, false>), dim3(N / 32),
-                       dim3(512), 0, stream, A, Q, scale, Cbf, M, N, K,
-                       lda);
-  } else {                                   // wo / wdown class
-    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<8, 1, false>), dim3(N / 16),
-                       dim3(512), 0, stream, A, Q, scale, Cbf, M, N, K,
-                       lda);
-  }
+  if (M <= 32)
+    qsa_skinny_gemm_fp8_launch_mt<2>(A, Q, scale, Cbf, M, N, K, lda, stream);
+  else                                       // M <= 64 (checked by the caller)
+    qsa_skinny_gemm_fp8_launch_mt<4>(A, Q, scale, Cbf, M, N, K, lda, stream);
 }
 
 extern "C" void qsa_skinny_gemm_fp8_probe_launch(
@@ -206,4 +230,25 @@ extern "C" void qsa_skinny_gemm_fp8_probe_launch(
   QSA_CASE(16, 1, false) QSA_CASE(16, 2, false) QSA_CASE(16, 4, false)
   QSA_CASE(4, 4, false) QSA_CASE(4, 8, false) QSA_CASE(2, 8, false)
 #undef QSA_CASE
+}
+
+// Sweep entry for the m-tile variants (tools/fp8_mtile_bench.py): returns 0
+// when (waves, tiles, mt) is not instantiated.
+extern "C" int qsa_skinny_gemm_fp8_probe_mt_launch(
+    const unsigned short* A, const unsigned char* Qf, const float* scale,
+    unsigned short* Cbf, int M, int N, long long K, long long lda,
+    int waves, int tiles, int mt, hipStream_t stream) {
+#define QSA_CASE(W, T, MTV)                                               \
+  if (waves == W && tiles == T && mt == MTV) {                            \
+    hipLaunchKernelGGL((qsa_skinny_gemm_fp8_t<W, T, false, MTV>),         \
+                       dim3(N / (16 * T)), dim3(W * 64), 0, stream, A,    \
+                       reinterpret_cast<const u32x4*>(Qf), scale, Cbf,    \
+                       M, N, K, lda);                                     \
+    return 1;                                                             \
+  }
+  QSA_CASE(2, 8, 2) QSA_CASE(8, 4, 2) QSA_CASE(8, 2, 2) QSA_CASE(8, 1, 2)
+  QSA_CASE(2, 8, 4) QSA_CASE(8, 4, 4) QSA_CASE(8, 2, 4) QSA_CASE(8, 1, 4)
+  // (8, 8, 4) does not fit 256 registers at 8 waves (39 VGPRs spill)
+#undef QSA_CASE
+  return 0;
 }
