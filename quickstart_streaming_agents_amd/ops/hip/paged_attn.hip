@@ -1,49 +1,40 @@
-// Paged-attention DECODE for CDNA4 (gfx950) — the K4 hot op, on MFMA.
+// Paged attention for CDNA4 (gfx950) on MFMA — the K4 hot op: decode,
+// prefill and the KV-cache writers over a paged KV cache in HBM3E.
 //
 // Replaces the reference's managed-LLM call (ML_PREDICT 'llm_textgen_model',
-// terraform/core/main.tf:461) with on-GPU batched decode attention over a
-// paged KV cache resident in 288 GB HBM3E.
+// terraform/core/main.tf:461) with on-GPU batched attention.
 //
-// Design (flash-decoding, one WAVE per (batch b, kv head, context split)):
-//   - All R GQA query heads of a kv head compute TOGETHER on the matrix
-//     cores: scores via mfma_f32_16x16x32_bf16 with A = K-tile
-//     [16 pos x 32 k] and B = Q [32 k x 16 heads] (heads pad to 16), PV
-//     via A = P [16 heads x 32 pos] (packed bf16, redistributed with 8
-//     cross-lane shuffles) and B = V^T [32 pos x 16 dims].  A VALU
-//     decode kernel pays ~16 VALU per 16 B of KV; this pays ~1 MFMA per
-//     1 KiB plus the online-softmax tail.
-//   - K cache layout [page, kvh, D/8, 64, 8] (d-major x8): the A-fragment
-//     read (lane = pos x k-slice) is one fully coalesced 1 KiB wave load.
-//   - V cache layout [page, kvh, D, 64] (TRANSPOSED, pos minor): the PV
-//     B-fragment read (lane = dim x pos-slice) is also one coalesced 1 KiB
-//     wave load.  Every KV byte is read exactly ONCE per (b, kvh) — the
-//     per-head VALU design re-read it R times.
-//   - Context splits fill the chip (grid = B*KVH*NS >= ~2k waves);
-//     unnormalized partials (o, m, l) merge in qsa_attn_reduce.
-//   - What the model runs is qsa_paged_attn_mfma_fused: this decomposition
-//     and arithmetic, bit for bit, with RoPE and the KV append folded in,
-//     the page's K/V fragment loads issued in batches one stage ahead of
-//     the MFMAs that consume them, and the splits merged inside the
-//     workgroup when NS <= 4.  qsa_rope_kv_append + qsa_paged_attn_mfma +
-//     qsa_attn_reduce remain as its oracle (QSA_DECODE_V1=1 runs them).
+// Cache layouts:
+//   K [page, kvh, D/8, 64, 8] (d-major x8): the score A-fragment read
+//     (lane = pos x k-slice) is one fully coalesced 1 KiB wave load.
+//   V [page, kvh, D, 64] (TRANSPOSED, pos minor): the PV B-fragment read
+//     (lane = dim x pos-slice) is also one coalesced 1 KiB wave load.
 //
-// The online softmax runs per head-column in registers: column max/sum
-// reduce with two shfl_xor hops (the 4 hi-lane groups of a column).
-//
-// Also in this file: the KV-cache writers (decode append, prefill scatter,
-// and the fused prefill rope + scatter qsa_rope_kv_scatter) and the two
-// varlen PREFILL attention kernels: qsa_paged_attn_prefill (one wave per
-// 16 q rows x head, fragments from global memory; the bit-exactness oracle
-// and the path for shapes the tiled kernel does not cover) and
-// qsa_paged_attn_prefill_tiled (one workgroup per 32/64 q rows x 4 heads,
-// K/V pages double-buffered in LDS; what LlamaModel prefill runs).
-#include "common.h"
-
-#define QSA_PAGE 64
-
-using bf16x8_a = __attribute__((ext_vector_type(8))) short;
-using f32x4_a = __attribute__((ext_vector_type(4))) float;
-using u32x4_a = __attribute__((ext_vector_type(4))) unsigned int;
+// The arithmetic is written once, in attn_core.h: mask + scale, the column
+// reduce, the online-softmax page update with its P repack, the score MFMAs
+// over global K fragments, the partials store, the split merge, the prefill
+// epilogue and the RoPE rotation.  Scores are mfma_f32_16x16x32_bf16 with
+// A = K-tile [16 pos x 32 k] and B = Q [32 k x 16 columns]; PV has
+// A = P [16 columns x 32 pos] (packed bf16) and B = V^T [32 pos x 16 dims].
+// A score column is a GQA head in decode (all R heads of a kv head compute
+// together, padded to 16, so every KV byte is read once per (b, kvh)) and a
+// q row in prefill.  The kernels differ only in when loads are issued, where
+// the K/V fragments come from and where the partials meet:
+//   qsa_paged_attn_mfma  flash-decoding, one WAVE per (batch, kv head, context
+//       split), fragments from global memory, fp32 partials merged by
+//       qsa_attn_reduce.  With qsa_rope_kv_append, the oracle of the fused
+//       kernel (QSA_DECODE_V1=1 runs them).
+//   qsa_paged_attn_mfma_fused  what the model runs: the same decomposition
+//       with RoPE and the KV append folded in, K/V fragment loads issued one
+//       stage ahead of the MFMAs, splits merged in LDS when NS <= 4.
+//   qsa_paged_attn_prefill  varlen prefill, one wave per 16 q rows x head,
+//       fragments from global memory: the encoder's path, the oracle of the
+//       tiled kernel and the path for shapes it does not cover.
+//   qsa_paged_attn_prefill_tiled  one workgroup per 32/64 q rows x 4 heads,
+//       K/V pages double-buffered in LDS; what LlamaModel prefill runs.
+// Also here: the KV-cache writers (decode append, prefill scatter and the
+// fused prefill rope + scatter qsa_rope_kv_scatter).
+#include "attn_core.h"
 
 template <int D>
 __global__ void __launch_bounds__(256)
@@ -56,7 +47,6 @@ qsa_paged_attn_mfma(const unsigned short* __restrict__ q,   // [B, QH, D]
                     float* __restrict__ part_ml,             // [B, QH, NS, 2]
                     float scale, int B, int QH, int KVH, int max_pages,
                     long long qstride, int NS) {
-  constexpr int KSTEPS = D / 32;      // QK^T k-steps (4 for D=128)
   constexpr int DTILES = D / 16;      // PV d-tiles (8 for D=128)
   const int wave = threadIdx.x >> 6;
   const int lane = threadIdx.x & 63;
@@ -85,14 +75,11 @@ qsa_paged_attn_mfma(const unsigned short* __restrict__ q,   // [B, QH, D]
     return;
   }
 
-  // ---- Q B-fragments: lane holds Q[head=col][k = ks*32 + hi*8 + e] ----
   const int qh_l = kvh * R + min(col, R - 1);   // clamp: pad heads compute
-  const unsigned short* qrow = q + (long long)b * qstride + (long long)qh_l * D;
-  bf16x8_a qf[KSTEPS];
-#pragma unroll
-  for (int ks = 0; ks < KSTEPS; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_a*>(qrow + ks * 32 + hi * 8);
+  bf16x8_a qf[D / 32];
+  qsa_load_q<D>(q + (long long)b * qstride + (long long)qh_l * D, hi, qf);
 
+  const qsa_lanes L = qsa_lanes_of(col, hi);
   float m = -3.0e38f, lsum = 0.f;
   f32x4_a o_acc[DTILES];
 #pragma unroll
@@ -108,136 +95,33 @@ qsa_paged_attn_mfma(const unsigned short* __restrict__ q,   // [B, QH, D]
         vc + (((long long)page * KVH + kvh) * D) * QSA_PAGE;
     const int nvalid = min(seqlen - pi * QSA_PAGE, QSA_PAGE);
 
-    // ---- scores: 4 pos-tiles x KSTEPS MFMAs ---------------------------
-    // A-frag: lane holds K[pos = pt*16 + col][k = ks*32 + hi*8 + e];
-    // K layout element (pos, k) at ((k/8)*64 + pos)*8 + k%8 ->
-    // 16 B at ((ks*4 + hi)*64 + pos)*8.
     f32x4_a sc[4];
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-      f32x4_a acc = {0.f, 0.f, 0.f, 0.f};
-      const int pos = pt * 16 + col;
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        const bf16x8_a kf = *reinterpret_cast<const bf16x8_a*>(
-            kbase + (((long long)(ks * 4 + hi) * QSA_PAGE) + pos) * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], acc,
-                                                      0, 0, 0);
-      }
-      sc[pt] = acc;
-    }
-    // scale + mask invalid positions; C layout: row pos = hi*4 + r,
-    // col head = lane&15 -> lane's r-th value is position pt*16 + hi*4 + r
-    float pagemax = -3.0e38f;
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int pos = pt * 16 + hi * 4 + r;
-        float v = (pos < nvalid) ? sc[pt][r] * scale : -3.0e38f;
-        sc[pt][r] = v;
-        pagemax = fmaxf(pagemax, v);
-      }
-    }
-    // column (per-head) max across the 4 hi groups
-    pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 16, QSA_WAVE));
-    pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 32, QSA_WAVE));
-    const float m_new = fmaxf(m, pagemax);
-    float alpha = __expf(m - m_new);
-    if (m <= -3.0e38f) alpha = 0.f;
-    m = m_new;
-    // o_acc element (dt, r) belongs to OUTPUT ROW hi*4 + r (the PV
-    // C-layout), while alpha lives per score COLUMN (this lane's l&15):
-    // fetch each row's own alpha from the lane holding that column —
-    // using the lane's own alpha zeroes/mis-scales other rows' history
-    // whenever per-row maxima diverge across pages
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float alpha_r = __shfl(alpha, hi * 4 + r, 16);
-#pragma unroll
-      for (int dt = 0; dt < DTILES; ++dt) o_acc[dt][r] *= alpha_r;
-    }
-    // P = exp(sc - m) (invalid -> 0), packed bf16x2 per tile quad
-    unsigned int ppk[8];   // tile pt -> 2 uints (4 bf16 = quads r0..3)
-    float psum = 0.f;
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-      float p0f = 0.f, p1f = 0.f, p2f = 0.f, p3f = 0.f;
-      if (sc[pt][0] > -1.0e38f) p0f = __expf(sc[pt][0] - m_new);
-      if (sc[pt][1] > -1.0e38f) p1f = __expf(sc[pt][1] - m_new);
-      if (sc[pt][2] > -1.0e38f) p2f = __expf(sc[pt][2] - m_new);
-      if (sc[pt][3] > -1.0e38f) p3f = __expf(sc[pt][3] - m_new);
-      psum += p0f + p1f + p2f + p3f;
-      ppk[pt * 2] = f32x2_to_bf16x2(p0f, p1f);
-      ppk[pt * 2 + 1] = f32x2_to_bf16x2(p2f, p3f);
-    }
-    psum += __shfl_xor(psum, 16, QSA_WAVE);
-    psum += __shfl_xor(psum, 32, QSA_WAVE);
-    lsum = lsum * alpha + psum;
+    qsa_scores_global<D>(kbase, qf, col, hi, sc);
+    const float pagemax = qsa_col_reduce<true>(
+        L, qsa_mask_scale<false>(sc, scale, hi, nvalid, 0, 0, true));
+    bf16x8_a pa[2];
+    qsa_page_update<DTILES>(L, sc, pagemax, m, lsum, o_acc, pa);
 
-    // ---- PV: two 32-pos halves ---------------------------------------
-    // A-frag needs lane (head=col, hi) to hold P[head][pos = hi*8 + e]:
-    // packed pairs come from source lanes (same col) with hi' = (2*hi)&3
-    // and (2*hi+1)&3, tile = half*2 + (hi>>1).
+    // ---- PV: two 32-pos halves; B-frag: lane holds
+    // V^T[pos = half*32 + hi*8 + e][d = dt*16 + col] = vc[.., d, pos]:
+    // 16 B at (d*64 + half*32 + hi*8)
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      // lane (col, hi) needs P[head=col][pos = half*32 + hi*8 + e]:
-      // tile T = half*2 + (hi>>1), quads (hi&1)*2 and (hi&1)*2+1 — i.e.
-      // source lanes (col, g) with g = (2*hi)&3 and (2*hi+1)&3.  __shfl
-      // evaluates the value expression in EACH lane, so the register
-      // index must be compile-time: shuffle both candidate tiles'
-      // packed regs and select by hi (guide rule 20: runtime-indexed
-      // arrays spill to scratch; and a runtime index would read the
-      // SOURCE lane's differently-computed tile).
-      const int src_a = col + (((2 * hi) & 3) << 4);
-      const int src_b = col + (((2 * hi + 1) & 3) << 4);
-      const int tA = half * 2;           // tile for hi 0,1
-      const int tB = half * 2 + 1;       // tile for hi 2,3
-      const unsigned int a0A = __shfl(ppk[tA * 2], src_a, QSA_WAVE);
-      const unsigned int a1A = __shfl(ppk[tA * 2 + 1], src_a, QSA_WAVE);
-      const unsigned int b0A = __shfl(ppk[tA * 2], src_b, QSA_WAVE);
-      const unsigned int b1A = __shfl(ppk[tA * 2 + 1], src_b, QSA_WAVE);
-      const unsigned int a0B = __shfl(ppk[tB * 2], src_a, QSA_WAVE);
-      const unsigned int a1B = __shfl(ppk[tB * 2 + 1], src_a, QSA_WAVE);
-      const unsigned int b0B = __shfl(ppk[tB * 2], src_b, QSA_WAVE);
-      const unsigned int b1B = __shfl(ppk[tB * 2 + 1], src_b, QSA_WAVE);
-      const bool lo = hi < 2;
-      bf16x8_a pa;
-      unsigned int* pa_u = reinterpret_cast<unsigned int*>(&pa);
-      pa_u[0] = lo ? a0A : a0B;
-      pa_u[1] = lo ? a1A : a1B;
-      pa_u[2] = lo ? b0A : b0B;
-      pa_u[3] = lo ? b1A : b1B;
 #pragma unroll
       for (int dt = 0; dt < DTILES; ++dt) {
-        // B-frag: lane holds V^T[pos = half*32 + hi*8 + e][d = dt*16+col]
-        // = vc[.., d, pos]: 16 B at (d*64 + half*32 + hi*8)
         const bf16x8_a vf = *reinterpret_cast<const bf16x8_a*>(
             vbase + ((long long)(dt * 16 + col) * QSA_PAGE) + half * 32 +
             hi * 8);
-        o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vf,
-                                                            o_acc[dt],
-                                                            0, 0, 0);
+        o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            pa[half], vf, o_acc[dt], 0, 0, 0);
       }
     }
   }
 
-  // ---- store partials: O C-layout row = head = hi*4 + r, col = dim ----
-  // lane (hi, col): holds O[head hi*4+r][d = dt*16 + col]
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int head = hi * 4 + r;
-    if (head < R) {
-      float* po = part_o +
-          (((long long)b * QH + kvh * R + head) * NS + split) * D;
-#pragma unroll
-      for (int dt = 0; dt < DTILES; ++dt)
-        po[dt * 16 + col] = o_acc[dt][r];
-    }
-  }
-  if (lane < R)
-    *reinterpret_cast<float2*>(pml_base + (long long)lane * NS * 2) =
-        make_float2(m, lsum);
+  qsa_store_partials<DTILES>(
+      o_acc, m, lsum, true,
+      part_o + (((long long)b * QH + kvh * R) * NS + split) * D, NS * D,
+      pml_base, NS * 2, R, lane);
 }
 
 template <int D>
@@ -248,19 +132,8 @@ qsa_attn_reduce(const float* __restrict__ part_o,   // [rows, NS, D]
                 int NS) {
   const long long row = blockIdx.x;
   const int d = threadIdx.x;  // D threads
-  const float* ml = part_ml + row * NS * 2;
-  float M = -3.0e38f;
-  for (int s = 0; s < NS; ++s)
-    if (ml[2 * s + 1] > 0.f) M = fmaxf(M, ml[2 * s]);
-  float L = 0.f, acc = 0.f;
-  for (int s = 0; s < NS; ++s) {
-    const float ls = ml[2 * s + 1];
-    if (ls <= 0.f) continue;
-    const float w = __expf(ml[2 * s] - M);
-    L += w * ls;
-    acc += w * part_o[(row * NS + s) * D + d];
-  }
-  const float v = (L > 0.f) ? acc / L : 0.f;
+  const float v = qsa_merge_splits(NS, part_ml + row * NS * 2, 2,
+                                   part_o + row * NS * D + d, D);
   out[row * D + d] = f32_to_bf16(v);
 }
 
@@ -288,15 +161,6 @@ extern "C" void qsa_paged_attn_mfma_launch(
   }
 }
 
-__device__ __forceinline__ float qsa_bperm_f(int byte_addr, float v) {
-  return __builtin_bit_cast(
-      float, __builtin_amdgcn_ds_bpermute(byte_addr, __builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ unsigned int qsa_bperm_u(int byte_addr,
-                                                   unsigned int v) {
-  return (unsigned int)__builtin_amdgcn_ds_bpermute(byte_addr, (int)v);
-}
-
 // One page of the fused decode loop.  PREFETCH is compile-time so that each
 // instantiation is straight-line code: with a runtime "is there a next
 // page" branch around the K loads the compiler's wait-count bookkeeping
@@ -305,20 +169,12 @@ template <int D, bool PREFETCH>
 __device__ __forceinline__ void qsa_decode_page(
     const unsigned short* kc, const unsigned short* vc, const int* btab,
     int pi, int p1, int seqlen, int KVH, int kvh, int koff, int voff,
-    int col, int hi, float scale, int& page, int& page_n,
+    const qsa_lanes& L, int hi, float scale, int& page, int& page_n,
     const bf16x8_a (&qf)[D / 32], bf16x8_a (&kfr)[4][D / 32],
     bf16x8_a (&vfr)[2][D / 16], f32x4_a (&o_acc)[D / 16], float& m,
     float& lsum) {
   constexpr int KSTEPS = D / 32;
   constexpr int DTILES = D / 16;
-  // lane shuffles as bare ds_bpermute on byte addresses (lane * 4): the
-  // same data movement as __shfl/__shfl_xor without their per-call range
-  // check, which costs VALU work and registers in this loop
-  const int lane4 = (hi * 16 + col) * 4;
-  const int x16 = lane4 ^ 64, x32 = lane4 ^ 128;
-  const int arow = hi * (16 + 4) * 4;              // lane hi*16 + hi*4 (+ r)
-  const int asrc_a = (col + (((2 * hi) & 3) << 4)) * 4;
-  const int asrc_b = (col + (((2 * hi + 1) & 3) << 4)) * 4;
   // ---- this page's V: in flight under the score MFMAs -----------------
   {
     // wave-uniform 64-bit base + 32-bit lane offset: one address VGPR
@@ -362,69 +218,18 @@ __device__ __forceinline__ void qsa_decode_page(
             kbase + (unsigned)(koff + (ks * 4 * QSA_PAGE + pt * 16) * 16));
   }
 
-  // ---- online softmax (qsa_paged_attn_mfma's, verbatim) ---------------
-  float pagemax = -3.0e38f;
-#pragma unroll
-  for (int pt = 0; pt < 4; ++pt) {
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int kpos = pt * 16 + hi * 4 + r;
-      float v = (kpos < nvalid) ? sc[pt][r] * scale : -3.0e38f;
-      sc[pt][r] = v;
-      pagemax = fmaxf(pagemax, v);
-    }
-  }
-  pagemax = fmaxf(pagemax, qsa_bperm_f(x16, pagemax));
-  pagemax = fmaxf(pagemax, qsa_bperm_f(x32, pagemax));
-  const float m_new = fmaxf(m, pagemax);
-  float alpha = __expf(m - m_new);
-  if (m <= -3.0e38f) alpha = 0.f;
-  m = m_new;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const float alpha_r = qsa_bperm_f(arow + r * 4, alpha);
-#pragma unroll
-    for (int dt = 0; dt < DTILES; ++dt) o_acc[dt][r] *= alpha_r;
-  }
-  unsigned int ppk[8];
-  float psum = 0.f;
-#pragma unroll
-  for (int pt = 0; pt < 4; ++pt) {
-    float p0f = 0.f, p1f = 0.f, p2f = 0.f, p3f = 0.f;
-    if (sc[pt][0] > -1.0e38f) p0f = __expf(sc[pt][0] - m_new);
-    if (sc[pt][1] > -1.0e38f) p1f = __expf(sc[pt][1] - m_new);
-    if (sc[pt][2] > -1.0e38f) p2f = __expf(sc[pt][2] - m_new);
-    if (sc[pt][3] > -1.0e38f) p3f = __expf(sc[pt][3] - m_new);
-    psum += p0f + p1f + p2f + p3f;
-    ppk[pt * 2] = f32x2_to_bf16x2(p0f, p1f);
-    ppk[pt * 2 + 1] = f32x2_to_bf16x2(p2f, p3f);
-  }
-  psum += qsa_bperm_f(x16, psum);
-  psum += qsa_bperm_f(x32, psum);
-  lsum = lsum * alpha + psum;
+  const float pagemax = qsa_col_reduce<true>(
+      L, qsa_mask_scale<false>(sc, scale, hi, nvalid, 0, 0, true));
+  bf16x8_a pa[2];
+  qsa_page_update<DTILES>(L, sc, pagemax, m, lsum, o_acc, pa);
 
-  // ---- PV: two 32-pos halves (P repack as qsa_paged_attn_mfma) --------
+  // ---- PV: two 32-pos halves ------------------------------------------
 #pragma unroll
-  for (int half = 0; half < 2; ++half) {
-    const int tA = half * 2;
-    const int tB = half * 2 + 1;
-    const unsigned int a0A = qsa_bperm_u(asrc_a, ppk[tA * 2]);
-    const unsigned int a1A = qsa_bperm_u(asrc_a, ppk[tA * 2 + 1]);
-    const unsigned int b0A = qsa_bperm_u(asrc_b, ppk[tA * 2]);
-    const unsigned int b1A = qsa_bperm_u(asrc_b, ppk[tA * 2 + 1]);
-    const unsigned int a0B = qsa_bperm_u(asrc_a, ppk[tB * 2]);
-    const unsigned int a1B = qsa_bperm_u(asrc_a, ppk[tB * 2 + 1]);
-    const unsigned int b0B = qsa_bperm_u(asrc_b, ppk[tB * 2]);
-    const unsigned int b1B = qsa_bperm_u(asrc_b, ppk[tB * 2 + 1]);
-    const bool lo = hi < 2;
-    const u32x4_a pu = {lo ? a0A : a0B, lo ? a1A : a1B,
-                        lo ? b0A : b0B, lo ? b1A : b1B};
-    const bf16x8_a pa = __builtin_bit_cast(bf16x8_a, pu);
+  for (int half = 0; half < 2; ++half)
 #pragma unroll
     for (int dt = 0; dt < DTILES; ++dt)
       o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
-          pa, vfr[half][dt], o_acc[dt], 0, 0, 0);
-  }
+          pa[half], vfr[half][dt], o_acc[dt], 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------
@@ -437,7 +242,7 @@ __device__ __forceinline__ void qsa_decode_page(
 //   RoPE     q arrives un-rotated.  A lane's Q fragments hold
 //            k = ks*32 + hi*8 + e, whose rotation partner k +- D/2 is
 //            fragment ks ^ (KSTEPS/2) of the SAME lane: rotated in registers
-//            with qsa_rope_kv_append's expressions, never written back.
+//            with qsa_rope8, never written back.
 //   append   the one wave whose split owns page (seq_len-1)/64 rotates the
 //            new k row, stores it and v into the cache, and makes the
 //            stores visible (workgroup fence) BEFORE it issues any K/V load
@@ -452,9 +257,9 @@ __device__ __forceinline__ void qsa_decode_page(
 //            only ever counts K/V fragments.  Prefetch never goes through
 //            an entry past p1-1.
 //   merge    NS <= 4: all splits of (b, kvh) are waves of this workgroup.
-//            (m, l, o) meet in LDS and every thread evaluates
-//            qsa_attn_reduce's formula in its order; bf16 out is written
-//            directly.  NS > 4: fp32 partials + qsa_attn_reduce as before.
+//            (m, l, o) meet in LDS and every thread merges one (head, d) with
+//            qsa_merge_splits, as qsa_attn_reduce does; bf16 out is written
+//            directly.  NS > 4: fp32 partials + qsa_attn_reduce.
 // WPE = waves per SIMD the register budget is held to (1: <= 512 unified
 // registers, 2: <= 256).
 // ---------------------------------------------------------------------------
@@ -520,30 +325,13 @@ qsa_paged_attn_mfma_fused(
       const int page = btab[npages - 1];
       const int pin = pos % QSA_PAGE;
       if (lane < D / 16) {
-        // 8 dims j*8.. and their +D/2 partners, as qsa_rope_kv_scatter
+        // 8 dims j*8.. and their +D/2 partners
         const int j = lane;
         const unsigned short* base =
             knew + (long long)b * kvstride + (long long)kvh * D + j * 8;
-        float c[8], s[8];
-        *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cosr + j * 8);
-        *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cosr + j * 8 + 4);
-        *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sinr + j * 8);
-        *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sinr + j * 8 + 4);
         uint4 a4 = *reinterpret_cast<const uint4*>(base);
         uint4 b4 = *reinterpret_cast<const uint4*>(base + HALF);
-        unsigned int* au = reinterpret_cast<unsigned int*>(&a4);
-        unsigned int* bu = reinterpret_cast<unsigned int*>(&b4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float2 x0 = bf16x2_to_f32x2(au[e]);
-          const float2 x1 = bf16x2_to_f32x2(bu[e]);
-          const float c0 = c[2 * e], c1 = c[2 * e + 1];
-          const float s0 = s[2 * e], s1 = s[2 * e + 1];
-          au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
-                  ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
-          bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
-                  ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
-        }
+        qsa_rope8(a4, b4, cosr + j * 8, sinr + j * 8);
         unsigned short* kdst = kc +
             (((((long long)page * KVH + kvh) * (D / 8) + j) * QSA_PAGE) + pin) * 8;
         *reinterpret_cast<uint4*>(kdst) = a4;
@@ -562,35 +350,17 @@ qsa_paged_attn_mfma_fused(
 
     // ---- Q B-fragments, rotated in registers ------------------------------
     const int qh_l = kvh * R + min(col, R - 1);   // clamp: pad heads compute
-    const unsigned short* qrow = q + (long long)b * qstride + (long long)qh_l * D;
     bf16x8_a qf[KSTEPS];
-#pragma unroll
-    for (int ks = 0; ks < KSTEPS; ++ks)
-      qf[ks] = *reinterpret_cast<const bf16x8_a*>(qrow + ks * 32 + hi * 8);
+    qsa_load_q<D>(q + (long long)b * qstride + (long long)qh_l * D, hi, qf);
 #pragma unroll
     for (int ks = 0; ks < KH; ++ks) {
-      float c[8], s[8];
-      const int o = ks * 32 + hi * 8;
-      *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cosr + o);
-      *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cosr + o + 4);
-      *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sinr + o);
-      *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sinr + o + 4);
-      u32x4_a au = __builtin_bit_cast(u32x4_a, qf[ks]);
-      u32x4_a bu = __builtin_bit_cast(u32x4_a, qf[ks + KH]);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float2 x0 = bf16x2_to_f32x2(au[e]);
-        const float2 x1 = bf16x2_to_f32x2(bu[e]);
-        const float c0 = c[2 * e], c1 = c[2 * e + 1];
-        const float s0 = s[2 * e], s1 = s[2 * e + 1];
-        au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
-                ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
-        bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
-                ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
-      }
-      qf[ks] = __builtin_bit_cast(bf16x8_a, au);
-      qf[ks + KH] = __builtin_bit_cast(bf16x8_a, bu);
+      uint4 a4 = __builtin_bit_cast(uint4, qf[ks]);
+      uint4 b4 = __builtin_bit_cast(uint4, qf[ks + KH]);
+      qsa_rope8(a4, b4, cosr + ks * 32 + hi * 8, sinr + ks * 32 + hi * 8);
+      qf[ks] = __builtin_bit_cast(bf16x8_a, a4);
+      qf[ks + KH] = __builtin_bit_cast(bf16x8_a, b4);
     }
+    const qsa_lanes L = qsa_lanes_of(col, hi);
 
     // ---- block-table entries: wave-uniform scalar loads, read one page
     // ahead of their use and never past entry p1-1 --------------------------
@@ -616,73 +386,35 @@ qsa_paged_attn_mfma_fused(
     // all pages but the last prefetch their successor's K
     for (int pi = p0; pi < p1 - 1; ++pi)
       qsa_decode_page<D, true>(kc, vc, btab, pi, p1, seqlen, KVH, kvh, koff,
-                               voff, col, hi, scale, page, page_n, qf, kfr,
+                               voff, L, hi, scale, page, page_n, qf, kfr,
                                vfr, o_acc, m, lsum);
     qsa_decode_page<D, false>(kc, vc, btab, p1 - 1, p1, seqlen, KVH, kvh,
-                              koff, voff, col, hi, scale, page, page_n, qf,
+                              koff, voff, L, hi, scale, page, page_n, qf,
                               kfr, vfr, o_acc, m, lsum);
   }
 
+  // every split slot writes its (m, l), real or empty; o only when live
   if (!merge) {
     // ---- NS > 4: fp32 partials for qsa_attn_reduce -------------------------
-    if (split >= NS) return;
-    float* pml_base =
-        part_ml + (((long long)b * QH + kvh * R) * NS + split) * 2;
-    if (live) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int head = hi * 4 + r;
-        if (head < R) {
-          float* po = part_o +
-              (((long long)b * QH + kvh * R + head) * NS + split) * D;
-#pragma unroll
-          for (int dt = 0; dt < DTILES; ++dt)
-            po[dt * 16 + col] = o_acc[dt][r];
-        }
-      }
-    }
-    if (lane < R)
-      *reinterpret_cast<float2*>(pml_base + (long long)lane * NS * 2) =
-          make_float2(m, lsum);
+    if (split < NS)
+      qsa_store_partials<DTILES>(
+          o_acc, m, lsum, live,
+          part_o + (((long long)b * QH + kvh * R) * NS + split) * D, NS * D,
+          part_ml + (((long long)b * QH + kvh * R) * NS + split) * 2, NS * 2,
+          R, lane);
     return;
   }
 
   // ---- NS <= 4: the splits are this workgroup's waves; merge through LDS --
-  if (split < NS) {
-    if (live) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int head = hi * 4 + r;
-        if (head < R) {
-          float* po = lds_o + (wave * 16 + head) * OP;
-#pragma unroll
-          for (int dt = 0; dt < DTILES; ++dt)
-            po[dt * 16 + col] = o_acc[dt][r];
-        }
-      }
-    }
-    if (lane < R)
-      *reinterpret_cast<float2*>(lds_ml + (wave * 16 + lane) * 2) =
-          make_float2(m, lsum);
-  }
+  if (split < NS)
+    qsa_store_partials<DTILES>(o_acc, m, lsum, live, lds_o + wave * 16 * OP,
+                               OP, lds_ml + wave * 16 * 2, 2, R, lane);
   __syncthreads();
-  // qsa_attn_reduce's formula, in its order, per (head, d)
   for (int idx = threadIdx.x; idx < R * D; idx += 256) {
     const int head = idx / D;
     const int d = idx % D;
-    float M = -3.0e38f;
-    for (int s = 0; s < NS; ++s)
-      if (lds_ml[(s * 16 + head) * 2 + 1] > 0.f)
-        M = fmaxf(M, lds_ml[(s * 16 + head) * 2]);
-    float L = 0.f, acc = 0.f;
-    for (int s = 0; s < NS; ++s) {
-      const float ls = lds_ml[(s * 16 + head) * 2 + 1];
-      if (ls <= 0.f) continue;
-      const float w = __expf(lds_ml[(s * 16 + head) * 2] - M);
-      L += w * ls;
-      acc += w * lds_o[(s * 16 + head) * OP + d];
-    }
-    const float v = (L > 0.f) ? acc / L : 0.f;
+    const float v = qsa_merge_splits(NS, lds_ml + head * 2, 16 * 2,
+                                     lds_o + head * OP + d, 16 * OP);
     out[((long long)b * QH + kvh * R + head) * D + d] = f32_to_bf16(v);
   }
 }
@@ -874,7 +606,6 @@ qsa_paged_attn_prefill(const unsigned short* __restrict__ q,   // [T, QH, D] str
                        unsigned short* __restrict__ out,       // [T, QH*D]
                        float scale, int QB, int QH, int KVH, int npmax,
                        long long qstride) {
-  constexpr int KSTEPS = D / 32;
   constexpr int DTILES = D / 16;
   const int lane = threadIdx.x & 63;
   const int gw = blockIdx.x * 4 + (threadIdx.x >> 6);  // global wave id
@@ -896,14 +627,12 @@ qsa_paged_attn_prefill(const unsigned short* __restrict__ q,   // [T, QH, D] str
   const int col = lane & 15;             // q-row column in the score tiles
   const int hi = lane >> 4;
 
-  // ---- Q B-fragments: lane holds Q[row pos0+col][k = ks*32 + hi*8+e] --
   const int qrow_l = min(pos0 + col, n_i - 1);   // clamp pad rows
-  const unsigned short* qrow =
-      q + (long long)(off + qrow_l) * qstride + (long long)qh * D;
-  bf16x8_a qf[KSTEPS];
-#pragma unroll
-  for (int ks = 0; ks < KSTEPS; ++ks)
-    qf[ks] = *reinterpret_cast<const bf16x8_a*>(qrow + ks * 32 + hi * 8);
+  bf16x8_a qf[D / 32];
+  qsa_load_q<D>(q + (long long)(off + qrow_l) * qstride + (long long)qh * D,
+                hi, qf);
+
+  const qsa_lanes L = qsa_lanes_of(col, hi);
 
   float m = -3.0e38f, lsum = 0.f;
   f32x4_a o_acc[DTILES];
@@ -928,123 +657,35 @@ qsa_paged_attn_prefill(const unsigned short* __restrict__ q,   // [T, QH, D] str
     const int nvalid = min(max_abs + 1 - pi * QSA_PAGE, QSA_PAGE);
 
     f32x4_a sc[4];
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-      f32x4_a acc = {0.f, 0.f, 0.f, 0.f};
-      const int pos = pt * 16 + col;
-#pragma unroll
-      for (int ks = 0; ks < KSTEPS; ++ks) {
-        const bf16x8_a kf = *reinterpret_cast<const bf16x8_a*>(
-            kbase + (((long long)(ks * 4 + hi) * QSA_PAGE) + pos) * 8);
-        acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[ks], acc,
-                                                      0, 0, 0);
-      }
-      sc[pt] = acc;
-    }
-    // mask: kpos (abs) must be <= start + qrow (abs) and < nvalid bound;
-    // C layout row kpos = pt*16 + hi*4 + r, col = q-row
-    const int qabs = start + pos0 + col;          // this column's row
-    float pagemax = -3.0e38f;
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int kpos = pt * 16 + hi * 4 + r;
-        const int kabs = pi * QSA_PAGE + kpos;
-        const bool ok = (kpos < nvalid) && (!CAUSAL || kabs <= qabs) &&
-                        (pos0 + col < n_i);
-        float v = ok ? sc[pt][r] * scale : -3.0e38f;
-        sc[pt][r] = v;
-        pagemax = fmaxf(pagemax, v);
-      }
-    }
-    pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 16, QSA_WAVE));
-    pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 32, QSA_WAVE));
+    qsa_scores_global<D>(kbase, qf, col, hi, sc);
+    const float pagemax = qsa_col_reduce<true>(
+        L, qsa_mask_scale<CAUSAL>(sc, scale, hi, nvalid, pi * QSA_PAGE,
+                                  start + pos0 + col, pos0 + col < n_i));
     // skip only when EVERY column is masked: the skip must be
     // wave-uniform — MFMA reads all 64 lanes' source registers
     // regardless of EXEC, so divergence around the PV MFMAs corrupts
     // active lanes' products
     if (__all(pagemax <= -3.0e38f)) continue;
-    const float m_new = fmaxf(m, pagemax);
-    float alpha = __expf(m - m_new);
-    if (m <= -3.0e38f) alpha = 0.f;
-    m = m_new;
-    // o_acc element (dt, r) belongs to OUTPUT ROW hi*4 + r (the PV
-    // C-layout), while alpha lives per score COLUMN (this lane's l&15):
-    // fetch each row's own alpha from the lane holding that column —
-    // using the lane's own alpha zeroes/mis-scales other rows' history
-    // whenever per-row maxima diverge across pages
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const float alpha_r = __shfl(alpha, hi * 4 + r, 16);
-#pragma unroll
-      for (int dt = 0; dt < DTILES; ++dt) o_acc[dt][r] *= alpha_r;
-    }
-    unsigned int ppk[8];
-    float psum = 0.f;
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-      float p0f = 0.f, p1f = 0.f, p2f = 0.f, p3f = 0.f;
-      if (sc[pt][0] > -1.0e38f) p0f = __expf(sc[pt][0] - m_new);
-      if (sc[pt][1] > -1.0e38f) p1f = __expf(sc[pt][1] - m_new);
-      if (sc[pt][2] > -1.0e38f) p2f = __expf(sc[pt][2] - m_new);
-      if (sc[pt][3] > -1.0e38f) p3f = __expf(sc[pt][3] - m_new);
-      psum += p0f + p1f + p2f + p3f;
-      ppk[pt * 2] = f32x2_to_bf16x2(p0f, p1f);
-      ppk[pt * 2 + 1] = f32x2_to_bf16x2(p2f, p3f);
-    }
-    psum += __shfl_xor(psum, 16, QSA_WAVE);
-    psum += __shfl_xor(psum, 32, QSA_WAVE);
-    lsum = lsum * alpha + psum;
+    bf16x8_a pa[2];
+    qsa_page_update<DTILES>(L, sc, pagemax, m, lsum, o_acc, pa);
 
 #pragma unroll
     for (int half = 0; half < 2; ++half) {
-      const int src_a = col + (((2 * hi) & 3) << 4);
-      const int src_b = col + (((2 * hi + 1) & 3) << 4);
-      const int tA = half * 2;
-      const int tB = half * 2 + 1;
-      const unsigned int a0A = __shfl(ppk[tA * 2], src_a, QSA_WAVE);
-      const unsigned int a1A = __shfl(ppk[tA * 2 + 1], src_a, QSA_WAVE);
-      const unsigned int b0A = __shfl(ppk[tA * 2], src_b, QSA_WAVE);
-      const unsigned int b1A = __shfl(ppk[tA * 2 + 1], src_b, QSA_WAVE);
-      const unsigned int a0B = __shfl(ppk[tB * 2], src_a, QSA_WAVE);
-      const unsigned int a1B = __shfl(ppk[tB * 2 + 1], src_a, QSA_WAVE);
-      const unsigned int b0B = __shfl(ppk[tB * 2], src_b, QSA_WAVE);
-      const unsigned int b1B = __shfl(ppk[tB * 2 + 1], src_b, QSA_WAVE);
-      const bool lo = hi < 2;
-      bf16x8_a pa;
-      unsigned int* pa_u = reinterpret_cast<unsigned int*>(&pa);
-      pa_u[0] = lo ? a0A : a0B;
-      pa_u[1] = lo ? a1A : a1B;
-      pa_u[2] = lo ? b0A : b0B;
-      pa_u[3] = lo ? b1A : b1B;
 #pragma unroll
       for (int dt = 0; dt < DTILES; ++dt) {
         const bf16x8_a vf = *reinterpret_cast<const bf16x8_a*>(
             vbase + ((long long)(dt * 16 + col) * QSA_PAGE) + half * 32 +
             hi * 8);
-        o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(pa, vf,
-                                                            o_acc[dt],
-                                                            0, 0, 0);
+        o_acc[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+            pa[half], vf, o_acc[dt], 0, 0, 0);
       }
     }
   }
 
-  // ---- epilogue: O C-layout row = q-row = hi*4 + r, col = dim ----------
-  // per-row 1/l lives in the lanes of its COLUMN; fetch via shfl
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int qr = hi * 4 + r;               // q-row this lane holds
-    const float lr = __shfl(lsum, qr, 16);   // lanes 0-15 hold cols 0-15
-    const float inv = (lr > 0.f) ? 1.f / lr : 0.f;
-    if (pos0 + qr < n_i) {
-      unsigned short* orow =
-          out + (long long)(off + pos0 + qr) * (QH * D) + (long long)qh * D;
-#pragma unroll
-      for (int dt = 0; dt < DTILES; ++dt)
-        orow[dt * 16 + col] = f32_to_bf16(o_acc[dt][r] * inv);
-    }
-  }
+  qsa_prefill_store<DTILES>(
+      L, o_acc, lsum,
+      out + (long long)(off + pos0) * (QH * D) + (long long)qh * D, QH * D,
+      n_i - pos0, col, hi);
 }
 
 extern "C" void qsa_paged_attn_prefill_launch(
@@ -1107,11 +748,11 @@ extern "C" void qsa_paged_attn_prefill_launch(
 //      conflict-free.
 //
 // Bit-exactness against the one-wave-per-block kernel: a sub-tile keeps its
-// own horizon (max_abs), processes exactly the pages the old kernel would
+// own horizon (max_abs), processes exactly the pages that kernel would
 // (pi < its own page count, and the same wave-uniform "whole page masked"
-// skip), and every accumulator sees the same MFMA/VALU sequence: the same
-// ks order, mask, scale, __expf, alpha, psum order, P packing shuffles, PV
-// order (half, then dt) and epilogue.
+// skip), and every accumulator sees the same sequence: the same ks order,
+// the shared mask, page update and epilogue, and the same PV order (half,
+// then dt).
 // ---------------------------------------------------------------------------
 template <int D, bool CAUSAL, int ROWS>
 __global__ void __launch_bounds__(256, ROWS == 32 ? 2 : 1)
@@ -1160,11 +801,8 @@ qsa_paged_attn_prefill_tiled(
   for (int s = 0; s < S; ++s) {
     const int pos0 = tpos0 + 16 * s;
     const int qrow_l = max(min(pos0 + col, n_i - 1), 0);   // clamp pad rows
-    const unsigned short* qrow =
-        q + (long long)(off + qrow_l) * qstride + (long long)qh * D;
-#pragma unroll
-    for (int ks = 0; ks < KSTEPS; ++ks)
-      qf[s][ks] = *reinterpret_cast<const bf16x8_a*>(qrow + ks * 32 + hi * 8);
+    qsa_load_q<D>(q + (long long)(off + qrow_l) * qstride + (long long)qh * D,
+                  hi, qf[s]);
     m[s] = -3.0e38f;
     lsum[s] = 0.f;
 #pragma unroll
@@ -1209,6 +847,7 @@ qsa_paged_attn_prefill_tiled(
   }
   __syncthreads();
 
+  const qsa_lanes L = qsa_lanes_of(col, hi);
   const int vsw = (col >> 1) & 7;          // V^T swizzle of this lane's rows
   for (int pi = 0; pi < np_wg; ++pi) {
     const int buf = pi & 1;
@@ -1239,7 +878,7 @@ qsa_paged_attn_prefill_tiled(
       }
     }
 
-    // ---- online softmax per sub-tile (lifted from the old kernel) -------
+    // ---- online softmax per sub-tile ------------------------------------
     bool pv[S];
     bf16x8_a pa[S][2];
 #pragma unroll
@@ -1248,71 +887,14 @@ qsa_paged_attn_prefill_tiled(
       if (!act[s]) continue;
       const int pos0 = tpos0 + 16 * s;
       const int nvalid = min(max_abs[s] + 1 - pi * QSA_PAGE, QSA_PAGE);
-      const int qabs = start + pos0 + col;
-      float pagemax = -3.0e38f;
-#pragma unroll
-      for (int pt = 0; pt < 4; ++pt) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int kpos = pt * 16 + hi * 4 + r;
-          const int kabs = pi * QSA_PAGE + kpos;
-          const bool ok = (kpos < nvalid) && (!CAUSAL || kabs <= qabs) &&
-                          (pos0 + col < n_i);
-          float v = ok ? sc[s][pt][r] * scale : -3.0e38f;
-          sc[s][pt][r] = v;
-          pagemax = fmaxf(pagemax, v);
-        }
-      }
-      pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 16, QSA_WAVE));
-      pagemax = fmaxf(pagemax, __shfl_xor(pagemax, 32, QSA_WAVE));
-      // wave-uniform skip of a page masked for EVERY column, as before
+      const float pagemax = qsa_col_reduce<true>(
+          L, qsa_mask_scale<CAUSAL>(sc[s], scale, hi, nvalid, pi * QSA_PAGE,
+                                    start + pos0 + col, pos0 + col < n_i));
+      // wave-uniform skip of a page masked for EVERY column
       if (__all(pagemax <= -3.0e38f)) continue;
       pv[s] = true;
-      const float m_new = fmaxf(m[s], pagemax);
-      float alpha = __expf(m[s] - m_new);
-      if (m[s] <= -3.0e38f) alpha = 0.f;
-      m[s] = m_new;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const float alpha_r = __shfl(alpha, hi * 4 + r, 16);
-#pragma unroll
-        for (int dt = 0; dt < DTILES; ++dt) o_acc[s][dt][r] *= alpha_r;
-      }
-      unsigned int ppk[8];
-      float psum = 0.f;
-#pragma unroll
-      for (int pt = 0; pt < 4; ++pt) {
-        float p0f = 0.f, p1f = 0.f, p2f = 0.f, p3f = 0.f;
-        if (sc[s][pt][0] > -1.0e38f) p0f = __expf(sc[s][pt][0] - m_new);
-        if (sc[s][pt][1] > -1.0e38f) p1f = __expf(sc[s][pt][1] - m_new);
-        if (sc[s][pt][2] > -1.0e38f) p2f = __expf(sc[s][pt][2] - m_new);
-        if (sc[s][pt][3] > -1.0e38f) p3f = __expf(sc[s][pt][3] - m_new);
-        psum += p0f + p1f + p2f + p3f;
-        ppk[pt * 2] = f32x2_to_bf16x2(p0f, p1f);
-        ppk[pt * 2 + 1] = f32x2_to_bf16x2(p2f, p3f);
-      }
-      psum += __shfl_xor(psum, 16, QSA_WAVE);
-      psum += __shfl_xor(psum, 32, QSA_WAVE);
-      lsum[s] = lsum[s] * alpha + psum;
-#pragma unroll
-      for (int half = 0; half < 2; ++half) {
-        const int src_a = col + (((2 * hi) & 3) << 4);
-        const int src_b = col + (((2 * hi + 1) & 3) << 4);
-        const int tA = half * 2;
-        const int tB = half * 2 + 1;
-        const unsigned int a0A = __shfl(ppk[tA * 2], src_a, QSA_WAVE);
-        const unsigned int a1A = __shfl(ppk[tA * 2 + 1], src_a, QSA_WAVE);
-        const unsigned int b0A = __shfl(ppk[tA * 2], src_b, QSA_WAVE);
-        const unsigned int b1A = __shfl(ppk[tA * 2 + 1], src_b, QSA_WAVE);
-        const unsigned int a0B = __shfl(ppk[tB * 2], src_a, QSA_WAVE);
-        const unsigned int a1B = __shfl(ppk[tB * 2 + 1], src_a, QSA_WAVE);
-        const unsigned int b0B = __shfl(ppk[tB * 2], src_b, QSA_WAVE);
-        const unsigned int b1B = __shfl(ppk[tB * 2 + 1], src_b, QSA_WAVE);
-        const bool lo = hi < 2;
-        const u32x4_a pu = {lo ? a0A : a0B, lo ? a1A : a1B,
-                            lo ? b0A : b0B, lo ? b1A : b1B};
-        pa[s][half] = __builtin_bit_cast(bf16x8_a, pu);
-      }
+      qsa_page_update<DTILES>(L, sc[s], pagemax, m[s], lsum[s], o_acc[s],
+                              pa[s]);
     }
 
     // ---- PV: one V^T fragment read feeds all live sub-tiles -------------
@@ -1337,23 +919,13 @@ qsa_paged_attn_prefill_tiled(
 #undef QSA_FETCH
 #undef QSA_STASH
 
-  // ---- epilogue per sub-tile (as the old kernel) --------------------------
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     const int pos0 = tpos0 + 16 * s;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int qr = hi * 4 + r;
-      const float lr = __shfl(lsum[s], qr, 16);
-      const float inv = (lr > 0.f) ? 1.f / lr : 0.f;
-      if (pos0 + qr < n_i) {
-        unsigned short* orow = out +
-            (long long)(off + pos0 + qr) * (QH * D) + (long long)qh * D;
-#pragma unroll
-        for (int dt = 0; dt < DTILES; ++dt)
-          orow[dt * 16 + col] = f32_to_bf16(o_acc[s][dt][r] * inv);
-      }
-    }
+    qsa_prefill_store<DTILES>(
+        L, o_acc[s], lsum[s],
+        out + (long long)(off + pos0) * (QH * D) + (long long)qh * D, QH * D,
+        n_i - pos0, col, hi);
   }
 }
 
@@ -1443,26 +1015,9 @@ qsa_rope_kv_scatter(unsigned short* __restrict__ q,        // [Tq, QH, D]
     if (t >= Tq) return;
     unsigned short* base = q + t * qstride + (long long)h * D + j * 8;
     const long long toff = (long long)pos[t] * half + j * 8;
-    float c[8], s[8];
-    *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cos_t + toff);
-    *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cos_t + toff + 4);
-    *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sin_t + toff);
-    *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sin_t + toff + 4);
     uint4 a = *reinterpret_cast<const uint4*>(base);
     uint4 b = *reinterpret_cast<const uint4*>(base + half);
-    unsigned int* au = reinterpret_cast<unsigned int*>(&a);
-    unsigned int* bu = reinterpret_cast<unsigned int*>(&b);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float2 x0 = bf16x2_to_f32x2(au[e]);
-      const float2 x1 = bf16x2_to_f32x2(bu[e]);
-      const float c0 = c[2 * e], c1 = c[2 * e + 1];
-      const float s0 = s[2 * e], s1 = s[2 * e + 1];
-      au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
-              ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
-      bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
-              ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
-    }
+    qsa_rope8(a, b, cos_t + toff, sin_t + toff);
     *reinterpret_cast<uint4*>(base) = a;
     *reinterpret_cast<uint4*>(base + half) = b;
     return;
@@ -1498,26 +1053,9 @@ qsa_rope_kv_scatter(unsigned short* __restrict__ q,        // [Tq, QH, D]
       const long long t = t0 + tl;
       const unsigned short* base = k + t * kvstride + (long long)kvh * D + j * 8;
       const long long toff = (long long)pos[t] * half + j * 8;
-      float c[8], s[8];
-      *reinterpret_cast<float4*>(c) = *reinterpret_cast<const float4*>(cos_t + toff);
-      *reinterpret_cast<float4*>(c + 4) = *reinterpret_cast<const float4*>(cos_t + toff + 4);
-      *reinterpret_cast<float4*>(s) = *reinterpret_cast<const float4*>(sin_t + toff);
-      *reinterpret_cast<float4*>(s + 4) = *reinterpret_cast<const float4*>(sin_t + toff + 4);
       uint4 a = *reinterpret_cast<const uint4*>(base);
       uint4 b = *reinterpret_cast<const uint4*>(base + half);
-      unsigned int* au = reinterpret_cast<unsigned int*>(&a);
-      unsigned int* bu = reinterpret_cast<unsigned int*>(&b);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float2 x0 = bf16x2_to_f32x2(au[e]);
-        const float2 x1 = bf16x2_to_f32x2(bu[e]);
-        const float c0 = c[2 * e], c1 = c[2 * e + 1];
-        const float s0 = s[2 * e], s1 = s[2 * e + 1];
-        au[e] = (unsigned int)f32_to_bf16(x0.x * c0 - x1.x * s0) |
-                ((unsigned int)f32_to_bf16(x0.y * c1 - x1.y * s1) << 16);
-        bu[e] = (unsigned int)f32_to_bf16(x0.x * s0 + x1.x * c0) |
-                ((unsigned int)f32_to_bf16(x0.y * s1 + x1.y * c1) << 16);
-      }
+      qsa_rope8(a, b, cos_t + toff, sin_t + toff);
       const int slot = slots[t];
       const long long page = slot / QSA_PAGE;
       const int pin = slot % QSA_PAGE;
