@@ -14,7 +14,10 @@ def rmsnorm_ref(x: torch.Tensor, w: torch.Tensor, eps: float = 1e-5,
     xf = x.float()
     res_out = None
     if residual is not None:
-        xf = xf + residual.float()
+        # the updated residual is stored in the input dtype and that stored
+        # (rounded) value is what gets normalised, as in the kernel and the
+        # CPU dispatch path
+        xf = (xf + residual.float()).to(x.dtype).float()
         res_out = xf
     var = xf.pow(2).mean(dim=-1, keepdim=True)
     y = xf * torch.rsqrt(var + eps) * w.float()
@@ -74,9 +77,18 @@ def paged_attn_ref(q: torch.Tensor, kc: torch.Tensor, vc: torch.Tensor,
 
 
 def topk_cosine_ref(queries: torch.Tensor, docs: torch.Tensor, k: int):
-    scores = queries.float() @ docs.float().T
-    s, i = torch.topk(scores, k, dim=-1)
-    return s, i.int()
+    """Top-k by (score descending, doc index ascending): a stable sort, so
+    equal scores rank, and are kept at the k boundary, by lowest index.
+    Each score is reduced on its own, in the same order for every doc, so
+    bit-identical rows score bit-equal (a BLAS matmul sums the rows of its
+    edge tiles in another order and breaks such ties at random)."""
+    if not 1 <= k <= docs.shape[0]:
+        raise RuntimeError(f"topk_cosine: k={k} out of range for "
+                           f"{docs.shape[0]} docs")
+    df = docs.float()
+    scores = torch.stack([(df * q).sum(-1) for q in queries.float()])
+    s, i = torch.sort(scores, dim=-1, descending=True, stable=True)
+    return s[:, :k].contiguous(), i[:, :k].int().contiguous()
 
 
 def softmax_rows_ref(scores: torch.Tensor, col_offset: int = 0,
@@ -93,12 +105,18 @@ def softmax_rows_ref(scores: torch.Tensor, col_offset: int = 0,
 
 def window_agg_ref(ts: torch.Tensor, key: torch.Tensor, value, t0: int,
                    win_ms: int, nwin: int, nkeys: int):
-    counts = torch.zeros(nkeys, nwin, dtype=torch.int32)
-    sums = torch.zeros(nkeys, nwin, dtype=torch.float32)
-    w = ((ts - t0) // win_ms)
+    """window = floor((ts - t0) / win_ms); events before t0 or at or past
+    window nwin are dropped.  f32 sums like the kernel's atomics."""
+    if win_ms <= 0 or nwin < 1:
+        raise RuntimeError("window_agg: win_ms > 0 and nwin >= 1")
+    if key.numel() != ts.numel() or \
+            (value is not None and value.numel() != ts.numel()):
+        raise RuntimeError("window_agg: one key (and value) per event")
+    w = torch.div(ts.long() - t0, win_ms, rounding_mode="floor")
     ok = (w >= 0) & (w < nwin)
-    for i in torch.nonzero(ok).flatten().tolist():
-        counts[key[i], w[i]] += 1
-        if value is not None:
-            sums[key[i], w[i]] += float(value[i])
-    return counts, sums
+    slot = key.long()[ok] * nwin + w[ok]
+    counts = torch.bincount(slot, minlength=nkeys * nwin).int()
+    sums = torch.zeros(nkeys * nwin, dtype=torch.float32)
+    if value is not None:
+        sums.index_add_(0, slot, value.float()[ok])
+    return counts.view(nkeys, nwin), sums.view(nkeys, nwin)

@@ -166,6 +166,11 @@ torch::Tensor swiglu(torch::Tensor gate, torch::Tensor up) {
   TORCH_CHECK(gate.stride(0) == up.stride(0), "row strides must match");
   const long long rows = gate.size(0), cols = gate.size(1);
   TORCH_CHECK(cols % 8 == 0, "cols % 8 == 0");
+  // 16-byte loads at row * stride + col
+  TORCH_CHECK(gate.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(gate.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(up.data_ptr()) % 16 == 0,
+              "swiglu: gate/up rows must be 16-byte aligned");
   auto y = torch::empty({rows, cols}, gate.options());
   const long long n = rows * cols;
   const int blocks = (int)std::min<long long>((n / 8 + 255) / 256, 8192);
@@ -706,6 +711,7 @@ std::vector<torch::Tensor> topk_cosine(torch::Tensor queries,
   const int Q = queries.size(0), D = queries.size(1), N = docs.size(0);
   TORCH_CHECK(docs.size(1) == D, "dim mismatch");
   TORCH_CHECK(k >= 1 && k <= 16, "k in [1,16]");
+  TORCH_CHECK(k <= N, "topk_cosine: k must not exceed the number of docs");
   const int nblk = std::max(1, (N + 2047) / 2048);
   auto opts_f = queries.options();
   auto opts_i = queries.options().dtype(at::kInt);
@@ -727,6 +733,11 @@ std::vector<torch::Tensor> window_agg(torch::Tensor ts, torch::Tensor key,
   CHK_DEV(ts); CHK_CONT(ts); CHK_I32(key);
   TORCH_CHECK(ts.scalar_type() == at::kLong, "ts must be i64");
   const long long n = ts.numel();
+  TORCH_CHECK(win_ms > 0, "window_agg: win_ms > 0");
+  TORCH_CHECK(nwin >= 1, "window_agg: nwin >= 1");
+  TORCH_CHECK(key.numel() == n, "window_agg: one key per event");
+  TORCH_CHECK(!value.has_value() || value.value().numel() == n,
+              "window_agg: one value per event");
   auto counts = torch::zeros({nkeys, nwin}, key.options());
   auto sums = torch::zeros({nkeys, nwin}, ts.options().dtype(at::kFloat));
   const float* vptr = nullptr;

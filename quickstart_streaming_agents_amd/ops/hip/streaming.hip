@@ -4,7 +4,8 @@
 
 // ---------------------------------------------------------------------------
 // Windowed aggregation: segmented count/sum by (key, window) over an event
-// batch.  window = (ts - t0) / win_ms; out slot = key * nwin + window.
+// batch.  window = floor((ts - t0) / win_ms), events with ts < t0 or
+// window >= nwin dropped; out slot = key * nwin + window.
 // The reference shape: TUMBLE(...) GROUP BY key (LAB3:99-133, LAB4:127-141).
 // ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256)
@@ -15,8 +16,11 @@ qsa_window_agg(const long long* __restrict__ ts, const int* __restrict__ key,
   long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long stride = (long long)gridDim.x * blockDim.x;
   for (; i < n; i += stride) {
-    const long long w = (ts[i] - t0) / win_ms;
-    if (w < 0 || w >= nwin) continue;
+    // floor, not C truncation: an event before t0 belongs to no window
+    const long long dt = ts[i] - t0;
+    if (dt < 0) continue;
+    const long long w = dt / win_ms;
+    if (w >= nwin) continue;
     const long long slot = (long long)key[i] * nwin + w;
     atomicAdd(counts + slot, 1);
     if (value && sums) atomicAdd(sums + slot, value[i]);
@@ -41,17 +45,20 @@ qsa_anomaly_batch(const float* __restrict__ series, const int* __restrict__ leng
   const int n = lengths[kidx];
 
   if (n < 6) {  // mean/std fallback (matches CPU path)
-    float sum = 0.f, sq = 0.f;
-    for (int i = lane; i < n; i += QSA_WAVE) {
-      sum += h[i];
-      sq = fmaf(h[i], h[i], sq);
-    }
+    // two passes: sum(h^2) - n*mean^2 cancels in f32 once the level is
+    // large against the spread (1000 +- 1 loses every digit of the std)
+    float sum = 0.f;
+    for (int i = lane; i < n; i += QSA_WAVE) sum += h[i];
     sum = wave_reduce_sum(sum);
+    const float mean = n > 0 ? sum / n : 0.f;
+    float sq = 0.f;
+    for (int i = lane; i < n; i += QSA_WAVE) {
+      const float d = h[i] - mean;
+      sq = fmaf(d, d, sq);
+    }
     sq = wave_reduce_sum(sq);
     if (lane == 0) {
-      const float mean = n > 0 ? sum / n : 0.f;
-      float sd = n > 1 ? sqrtf(fmaxf((sq - n * mean * mean) / (n - 1), 0.f))
-                       : fabsf(mean) + 1.f;
+      float sd = n > 1 ? sqrtf(sq / (n - 1)) : fabsf(mean) + 1.f;
       forecast[kidx] = mean;
       pred_se[kidx] = fmaxf(sd, 1e-9f);
       dof_out[kidx] = max(n - 1, 1);

@@ -15,6 +15,14 @@
 #define QSA_TOPK_MAX 16
 #define QSA_DOCS_PER_BLOCK 2048
 
+// Result order: score descending, then document id ascending, so equal
+// scores rank (and survive the k boundary) by lowest id whichever wave or
+// block scanned them.  The empty-slot id -1 compares as the largest id.
+__device__ __forceinline__ bool qsa_topk_before(float sa, int ia, float sb,
+                                                int ib) {
+  return sa > sb || (sa == sb && (unsigned int)ia < (unsigned int)ib);
+}
+
 __global__ void __launch_bounds__(256)
 qsa_topk_stage1(const float* __restrict__ queries,  // [Q, D] L2-normalized
                 const float* __restrict__ docs,     // [N, D] L2-normalized
@@ -76,9 +84,10 @@ qsa_topk_stage1(const float* __restrict__ queries,  // [Q, D] L2-normalized
       for (int j = 0; j < k; ++j) {
         const float sc = wsc[w * QSA_TOPK_MAX + j];
         const int id = wid[w * QSA_TOPK_MAX + j];
-        if (sc > out_s[k - 1]) {
+        if (qsa_topk_before(sc, id, out_s[k - 1], out_i[k - 1])) {
           int t = k - 1;
-          while (t > 0 && out_s[t - 1] < sc) {
+          while (t > 0 &&
+                 qsa_topk_before(sc, id, out_s[t - 1], out_i[t - 1])) {
             out_s[t] = out_s[t - 1];
             out_i[t] = out_i[t - 1];
             --t;
@@ -108,15 +117,16 @@ qsa_topk_stage2(const float* __restrict__ cand_scores,  // [Q, nblk, k]
   const int* ci = cand_ids + (long long)qi * nblk * k;
   for (int t = 0; t < nblk * k; ++t) {
     const float sc = cs[t];
-    if (sc > out_s[k - 1]) {
+    const int id = ci[t];
+    if (qsa_topk_before(sc, id, out_s[k - 1], out_i[k - 1])) {
       int j = k - 1;
-      while (j > 0 && out_s[j - 1] < sc) {
+      while (j > 0 && qsa_topk_before(sc, id, out_s[j - 1], out_i[j - 1])) {
         out_s[j] = out_s[j - 1];
         out_i[j] = out_i[j - 1];
         --j;
       }
       out_s[j] = sc;
-      out_i[j] = ci[t];
+      out_i[j] = id;
     }
   }
   for (int j = 0; j < k; ++j) {

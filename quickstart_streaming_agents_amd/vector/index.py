@@ -167,7 +167,10 @@ class VectorIndex:
         k_eff = min(k, len(self))
         if len(q) >= 16:
             # large query batches are GEMM-shaped: one MFMA matmul over
-            # the HBM matrix + top-k beats per-query matrix re-streaming
+            # the HBM matrix + top-k beats per-query matrix re-streaming.
+            # torch.topk promises no order among equal scores (duplicate
+            # rows); the kernel path and the CPU reference rank the lowest
+            # document index first.
             scores_all = qt @ docs.T
             scores, idx = torch.topk(scores_all, k_eff, dim=1)
             idx = idx.int()

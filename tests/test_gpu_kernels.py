@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from quickstart_streaming_agents_amd.ops import cpu_ref
+from test_kernel_edges import assert_bf16_close, rmsnorm_ref64
 
 pytestmark = pytest.mark.gpu
 
@@ -28,8 +29,11 @@ def test_rmsnorm(ext):
     x = torch.randn(33, 4096, dtype=torch.bfloat16, device=dev())
     w = torch.randn(4096, dtype=torch.bfloat16, device=dev())
     y = ext.rmsnorm(x, w, 1e-5)
-    ref = cpu_ref.rmsnorm_ref(x.cpu(), w.cpu())
-    torch.testing.assert_close(y.float().cpu(), ref, atol=5e-2, rtol=5e-2)
+    ref, _ = rmsnorm_ref64(x.cpu(), w.cpu(), 1e-5)
+    assert_bf16_close(y, ref, "rmsnorm")
+    # the f32 reference agrees with the f64 one far inside a bf16 ulp
+    torch.testing.assert_close(cpu_ref.rmsnorm_ref(x.cpu(), w.cpu()).double(),
+                               ref, atol=1e-6, rtol=1e-5)
 
 
 def test_rmsnorm_residual(ext):
@@ -38,9 +42,13 @@ def test_rmsnorm_residual(ext):
     res = torch.randn(17, 4096, dtype=torch.bfloat16, device=dev())
     w = torch.randn(4096, dtype=torch.bfloat16, device=dev())
     ref_y, ref_res = cpu_ref.rmsnorm_ref(x.cpu(), w.cpu(), residual=res.cpu())
+    ref64, r = rmsnorm_ref64(x.cpu(), w.cpu(), 1e-5, res.cpu())
     y = ext.rmsnorm_residual(x, res, w, 1e-5)
-    torch.testing.assert_close(y.float().cpu(), ref_y, atol=5e-2, rtol=5e-2)
-    torch.testing.assert_close(res.float().cpu(), ref_res, atol=3e-2, rtol=3e-2)
+    assert_bf16_close(y, ref64, "rmsnorm_residual")
+    # updated residual: one exact f32 add, one rounding -> bit-equal
+    assert torch.equal(res.cpu(), r)
+    assert torch.equal(ref_res, r.float())
+    torch.testing.assert_close(ref_y.double(), ref64, atol=1e-6, rtol=1e-5)
 
 
 def test_swiglu(ext):
@@ -136,6 +144,18 @@ def test_kv_scatter(ext):
     slot = int(slots[t])
     got = vc[slot // 64, :, :, slot % 64].float().cpu()
     torch.testing.assert_close(got, vnew[t].float().cpu(), atol=1e-3, rtol=1e-3)
+    # every token's K and V bit-equal at its slot (slots 28..127 cross the
+    # page-0 / page-1 boundary), every other slot of the 4 pages still zero
+    kc_h, vc_h = kc.cpu(), vc.cpu()
+    knew_h, vnew_h = knew.cpu(), vnew.cpu()
+    for t, slot in enumerate(slots.tolist()):
+        page, off = slot // 64, slot % 64
+        assert torch.equal(kc_h[page, :, :, off, :].reshape(KVH, D),
+                           knew_h[t]), f"K of token {t}"
+        assert torch.equal(vc_h[page, :, :, off], vnew_h[t]), f"V of token {t}"
+        kc_h[page, :, :, off, :] = 0
+        vc_h[page, :, :, off] = 0
+    assert not kc_h.any() and not vc_h.any()
 
 
 def test_topk_cosine(ext):
