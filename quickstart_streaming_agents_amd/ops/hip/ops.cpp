@@ -510,10 +510,19 @@ torch::Tensor pack_weight_frag(torch::Tensor w) {
       .permute({0, 2, 1, 3}).contiguous();
 }
 
+// The weight-streaming GEMMs load 16 B from A + row * lda + k (k % 8 == 0).
+static inline void chk_gemm_a_aligned(const torch::Tensor& a,
+                                      const char* op) {
+  TORCH_CHECK(a.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
+              op, ": a rows must be 16-byte aligned");
+}
+
 torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor wf, long N, long K) {
   // C[M,N] = a[M,K] @ W^T with W pre-packed by pack_weight_frag.
-  CHK_DEV(a); CHK_BF16(a); CHK_BF16(wf); CHK_CONT(wf);
+  CHK_DEV(a); CHK_BF16(a); CHK_DEV(wf); CHK_BF16(wf); CHK_CONT(wf);
   TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
+  chk_gemm_a_aligned(a, "skinny_gemm");
   const int M = a.size(0);
   TORCH_CHECK(M >= 1 && M <= 32, "skinny_gemm: M in [1,32]");
   TORCH_CHECK(a.size(1) == K, "K mismatch");
@@ -540,11 +549,12 @@ torch::Tensor gemm_fp8_batch(torch::Tensor a, torch::Tensor qf,
                              torch::Tensor scale, long N, long K,
                              long splitk) {
   // C[M,N] = a @ (scale * dequant(Q))^T for decode batches 32 < M <= 256
-  CHK_DEV(a); CHK_BF16(a); CHK_CONT(qf);
+  CHK_DEV(a); CHK_BF16(a); CHK_DEV(qf); CHK_CONT(qf);
   TORCH_CHECK(qf.scalar_type() == torch::kUInt8, "qf must be uint8 (fp8)");
   TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.is_cuda() &&
                   scale.is_contiguous() && scale.numel() == N, "scale");
   TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
+  chk_gemm_a_aligned(a, "gemm_fp8_batch");
   const int M = a.size(0);
   TORCH_CHECK(M >= 1 && M <= 256, "gemm_fp8_batch: M in [1,256]");
   TORCH_CHECK(a.size(1) == K, "K mismatch");
@@ -611,12 +621,13 @@ torch::Tensor skinny_gemm_fp8(torch::Tensor a, torch::Tensor qf,
                               torch::Tensor scale, long N, long K) {
   // C[M,N] = a @ (scale[N] * dequant(Q))^T; Q pre-packed fp8 e4m3 in the
   // fragment-pair-major stream layout (skinny_gemm_fp8.hip header).
-  CHK_DEV(a); CHK_BF16(a); CHK_CONT(qf);
+  CHK_DEV(a); CHK_BF16(a); CHK_DEV(qf); CHK_CONT(qf);
   TORCH_CHECK(qf.scalar_type() == torch::kUInt8, "qf must be uint8 (fp8)");
   TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.is_cuda() &&
                   scale.is_contiguous() && scale.numel() == N,
               "scale must be f32 [N] on device");
   TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
+  chk_gemm_a_aligned(a, "skinny_gemm_fp8");
   const int M = a.size(0);
   TORCH_CHECK(M >= 1 && M <= 64, "skinny_gemm_fp8: M in [1,64]");
   TORCH_CHECK(a.size(1) == K, "K mismatch");
