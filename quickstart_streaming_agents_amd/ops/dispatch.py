@@ -224,7 +224,7 @@ def skinny_linear(x: torch.Tensor, wf: torch.Tensor, n: int,
 
 def pack_weight_fp8(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """[N,K] bf16 -> (fp8-e4m3 fragment-pair-major stream as uint8,
-    per-channel f32 scales).  Layout doc: ops/hip/skinny_gemm_fp8.hip."""
+    per-channel f32 scales).  Layout doc: ops/hip/gemm_core.h."""
     n, k = w.shape
     assert n % 16 == 0 and k % 256 == 0
     wf = w.float()
@@ -274,7 +274,9 @@ def skinny_fp8_class(n: int, k: int) -> str:
     """The fp8 skinny launcher's shape class for an [n, k] weight
     (ops/hip/skinny_gemm_fp8.hip), its last class split by K: the launch
     is the same for wo and wdown, the comparison with rocBLAS is not.
-    Mirrors qsa_skinny_gemm_fp8_launch_mt: change the two together."""
+    The CPU-only copy of the extension's skinny_fp8_class;
+    tests/test_gpu_gemm_edges.py test_skinny_fp8_class_agrees compares
+    the two."""
     if n % 128 == 0 and n >= 65536:
         return "lm_head"
     if n % 64 == 0 and n >= 16384:

@@ -10,7 +10,7 @@
 //   * Workgroup = 4 waves, C block [16*M_FRAGS, 64]: wave w owns the
 //     16-column n-tile nt = blockIdx.x*4 + w for the FULL M range, so
 //     its weight fragments are private (one 16-B dwordx4 per 64-k step,
-//     the fragment-pair-major layout of skinny_gemm_fp8.hip) while the
+//     the fp8 fragment-pair-major stream of gemm_core.h) while the
 //     A tile in LDS is shared by all 4 waves.
 //   * A tile [16*M_FRAGS][64] bf16, row-padded to 80 elements: the
 //     (40*row + 4*hi) mod 64 bank pattern makes both the cooperative
@@ -20,40 +20,16 @@
 //     (qkv/wo/wdown at N/64 < 256 workgroups): each split accumulates
 //     into its own f32 slab; qsa_splitk_reduce sums the slabs, applies
 //     the per-channel scale and casts to bf16.
-//   * In-kernel dequant is the exact cvt_pk_f32_fp8 + v_perm path shared
-//     with the skinny kernel (fp8 -> bf16 is lossless).
+//   * In-kernel dequant is gemm_core.h's exact cvt_pk_f32_fp8 + v_perm
+//     path, shared with the skinny kernel (fp8 -> bf16 is lossless).
 //
 // At M=192 these shapes sit at the compute/bandwidth crossover
 // (wgu: 45 GFLOP ~ 22 us at the bf16 MFMA rate vs 18.6 us fp8 stream),
 // so the ceiling is ~max(stream, MFMA) — the kernel's job is to pin the
 // stream at 1x W bytes and keep the MFMA pipe fed from LDS.
-#include "common.h"
-
-using bf16x8 = __attribute__((ext_vector_type(8))) short;
-using f32x2v = __attribute__((ext_vector_type(2))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned int;
+#include "gemm_core.h"
 
 #define QSA_GB_PAD 80   // LDS row pitch (elements) for the A tile
-
-__device__ __forceinline__ bf16x8 qsa_gb_cvt(unsigned int a,
-                                             unsigned int b) {
-  f32x2v f01 = __builtin_amdgcn_cvt_pk_f32_fp8(a, false);
-  f32x2v f23 = __builtin_amdgcn_cvt_pk_f32_fp8(a, true);
-  f32x2v f45 = __builtin_amdgcn_cvt_pk_f32_fp8(b, false);
-  f32x2v f67 = __builtin_amdgcn_cvt_pk_f32_fp8(b, true);
-  union { unsigned int u; float f; } u0, u1;
-  union { unsigned int u[4]; bf16x8 v; } out;
-  u0.f = f01.x; u1.f = f01.y;
-  out.u[0] = __builtin_amdgcn_perm(u1.u, u0.u, 0x07060302u);
-  u0.f = f23.x; u1.f = f23.y;
-  out.u[1] = __builtin_amdgcn_perm(u1.u, u0.u, 0x07060302u);
-  u0.f = f45.x; u1.f = f45.y;
-  out.u[2] = __builtin_amdgcn_perm(u1.u, u0.u, 0x07060302u);
-  u0.f = f67.x; u1.f = f67.y;
-  out.u[3] = __builtin_amdgcn_perm(u1.u, u0.u, 0x07060302u);
-  return out.v;
-}
 
 template <int M_FRAGS, int SPLITK, int NT>
 __global__ void __launch_bounds__(256)
@@ -86,13 +62,11 @@ qsa_gemm_fp8_batch(const unsigned short* __restrict__ A,  // [M,K] bf16
     for (int m = 0; m < M_FRAGS; ++m)
       acc[t][m] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-  // W stream bases for this wave's n-tiles (16 B per 64-k block; layout
-  // identical to skinny_gemm_fp8.hip)
+  // W stream bases for this wave's n-tiles (16 B per 64-k block)
+  using W = qsa_fp8_stream;
   const u32x4* qbase[NT];
 #pragma unroll
-  for (int t = 0; t < NT; ++t)
-    qbase[t] = Qf + ((long long)(nt16 + t) * (K >> 6)) * 64 +
-               (long long)((lane & 15) * 4 + (lane >> 4));
+  for (int t = 0; t < NT; ++t) qbase[t] = W::lane_base(Qf, nt16 + t, K, lane);
 
   // cooperative A fill map: chunk c covers row c/8, 16 B at col (c%8)*8
   constexpr int CHUNKS = R * 8;            // 16-B chunks per 64-k tile
@@ -111,16 +85,15 @@ qsa_gemm_fp8_batch(const unsigned short* __restrict__ A,  // [M,K] bf16
 #pragma unroll
     for (int i = 0; i < PER_T; ++i) {
       const int row = frow + i * 32;
-      const int arow = min(row, M - 1);
       const bf16x8 v = *reinterpret_cast<const bf16x8*>(
-          A + (long long)arow * lda + k0 + fc8);
+          qsa_a_row(A, row, M, lda) + k0 + fc8);
       *reinterpret_cast<bf16x8*>(&atile[0][row * QSA_GB_PAD + fc8]) = v;
     }
   }
   u32x4 q[NT];
 #pragma unroll
   for (int t = 0; t < NT; ++t)
-    q[t] = __builtin_nontemporal_load(qbase[t] + kb0 * 64);
+    q[t] = W::load<true>(qbase[t] + W::block_off(kb0));
   __syncthreads();
 
   for (long long kb = kb0; kb < kb1; ++kb) {
@@ -133,12 +106,11 @@ qsa_gemm_fp8_batch(const unsigned short* __restrict__ A,  // [M,K] bf16
       const long long kn = (kb + 1) << 6;
 #pragma unroll
       for (int t = 0; t < NT; ++t)
-        q_next[t] = __builtin_nontemporal_load(qbase[t] + (kb + 1) * 64);
+        q_next[t] = W::load<true>(qbase[t] + W::block_off(kb + 1));
 #pragma unroll
       for (int i = 0; i < PER_T; ++i) {
-        const int arow = min(frow + i * 32, M - 1);
         stage[i] = *reinterpret_cast<const bf16x8*>(
-            A + (long long)arow * lda + kn + fc8);
+            qsa_a_row(A, frow + i * 32, M, lda) + kn + fc8);
       }
     }
     // ---- this wave's W fragments + MFMA sweep over the m-frags --------
@@ -148,10 +120,7 @@ qsa_gemm_fp8_batch(const unsigned short* __restrict__ A,  // [M,K] bf16
     // read -> waitcnt -> MFMA per fragment (the hipcc default here)
     bf16x8 w0[NT], w1[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-      w0[t] = qsa_gb_cvt(q[t].x, q[t].y);     // k0 .. +32
-      w1[t] = qsa_gb_cvt(q[t].z, q[t].w);     // k0+32 .. +64
-    }
+    for (int t = 0; t < NT; ++t) W::frags(q[t], w0[t], w1[t]);
     const unsigned short* abase = &atile[cur][col * QSA_GB_PAD + hi * 8];
 #define QSA_GB_RD0(m) \
   (*reinterpret_cast<const bf16x8*>(abase + (m) * 16 * QSA_GB_PAD))
@@ -203,11 +172,8 @@ qsa_gemm_fp8_batch(const unsigned short* __restrict__ A,  // [M,K] bf16
 #pragma unroll
       for (int m = 0; m < M_FRAGS; ++m) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = m * 16 + hi * 4 + r;
-          if (row < M)
-            Cbf[(long long)row * N + ncol] = f32_to_bf16(acc[t][m][r] * s);
-        }
+        for (int r = 0; r < 4; ++r)
+          qsa_store_c(Cbf, m * 16 + hi * 4 + r, ncol, M, N, acc[t][m][r] * s);
       }
     } else {
       float* slab = ws + (long long)blockIdx.y * M * N;

@@ -82,24 +82,17 @@ extern "C" void qsa_skinny_gemm_launch(const unsigned short*,
                                        const unsigned short*, unsigned short*,
                                        int, int, long long, long long,
                                        hipStream_t);
-extern "C" void qsa_skinny_gemm_probe_launch(const unsigned short*,
-                                             const unsigned short*,
-                                             unsigned short*, int, int,
-                                             long long, long long, int, int,
-                                             int, hipStream_t);
-extern "C" void qsa_skinny_gemm_fp8_launch(const unsigned short*,
-                                           const unsigned char*,
-                                           const float*, unsigned short*,
-                                           int, int, long long, long long,
-                                           hipStream_t);
-extern "C" void qsa_skinny_gemm_fp8_probe_launch(
+extern "C" int qsa_skinny_gemm_probe_launch(
+    const unsigned short*, const unsigned short*, unsigned short*, int, int,
+    long long, long long, int, int, int, hipStream_t);
+extern "C" void qsa_skinny_gemm_fp8_launch(
     const unsigned short*, const unsigned char*, const float*,
-    unsigned short*, int, int, long long, long long, int, int, int,
-    hipStream_t);
-extern "C" int qsa_skinny_gemm_fp8_probe_mt_launch(
+    unsigned short*, int, int, long long, long long, hipStream_t);
+extern "C" int qsa_skinny_gemm_fp8_config_launch(
     const unsigned short*, const unsigned char*, const float*,
-    unsigned short*, int, int, long long, long long, int, int, int,
+    unsigned short*, int, int, long long, long long, int, int, int, int,
     hipStream_t);
+extern "C" const char* qsa_skinny_fp8_class(int, long long);
 extern "C" void qsa_greedy_sample_launch(
     const unsigned short*, int, long long, int, int, int, const long long*,
     const unsigned char*, int, long long*, long long*, long long, int,
@@ -510,58 +503,119 @@ torch::Tensor pack_weight_frag(torch::Tensor w) {
       .permute({0, 2, 1, 3}).contiguous();
 }
 
-// The weight-streaming GEMMs load 16 B from A + row * lda + k (k % 8 == 0).
-static inline void chk_gemm_a_aligned(const torch::Tensor& a,
-                                      const char* op) {
+// ---- weight-streaming GEMMs: checks shared by the six bindings -------------
+// Activations a[M,K] of `op`, M in [1, max_m]; the kernels load 16 B from
+// A + row * lda + k (k % 8 == 0).  Returns M.
+static int chk_gemm_a(const torch::Tensor& a, long K, long max_m,
+                      const char* op) {
+  CHK_DEV(a); CHK_BF16(a);
+  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
   TORCH_CHECK(a.stride(0) % 8 == 0 &&
               reinterpret_cast<uintptr_t>(a.data_ptr()) % 16 == 0,
               op, ": a rows must be 16-byte aligned");
+  const long M = a.size(0);
+  TORCH_CHECK(M >= 1 && M <= max_m, op, ": M in [1,", max_m, "]");
+  TORCH_CHECK(a.size(1) == K, "K mismatch");
+  return (int)M;
+}
+
+// A skinny launch with `tiles` 16-column n-tiles per workgroup: checks a and
+// the shape, returns the [M, N] output.
+static torch::Tensor skinny_out(const torch::Tensor& a, long N, long K,
+                                long tiles, long max_m, const char* op) {
+  const int M = chk_gemm_a(a, K, max_m, op);
+  TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "K%256==0, N%16==0");
+  TORCH_CHECK(tiles >= 1 && N % (16 * tiles) == 0, "N%(16*tiles)==0");
+  return torch::empty({M, (long long)N}, a.options());
+}
+
+static void chk_bf16_stream(const torch::Tensor& wf, long N, long K) {
+  CHK_DEV(wf); CHK_BF16(wf); CHK_CONT(wf);
+  TORCH_CHECK(wf.numel() == (long long)N * K, "wf size");
+}
+
+// fp8 e4m3 stream (layout: gemm_core.h) and its per-channel scales.
+static void chk_fp8_stream(const torch::Tensor& qf,
+                           const torch::Tensor& scale, long N, long K) {
+  CHK_DEV(qf); CHK_CONT(qf);
+  TORCH_CHECK(qf.scalar_type() == torch::kUInt8, "qf must be uint8 (fp8)");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.is_cuda() &&
+                  scale.is_contiguous() && scale.numel() == N,
+              "scale must be f32 [N] on device");
+  TORCH_CHECK(qf.numel() == (long long)N * K, "qf size");
 }
 
 torch::Tensor skinny_gemm(torch::Tensor a, torch::Tensor wf, long N, long K) {
   // C[M,N] = a[M,K] @ W^T with W pre-packed by pack_weight_frag.
-  CHK_DEV(a); CHK_BF16(a); CHK_DEV(wf); CHK_BF16(wf); CHK_CONT(wf);
-  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
-  chk_gemm_a_aligned(a, "skinny_gemm");
-  const int M = a.size(0);
-  TORCH_CHECK(M >= 1 && M <= 32, "skinny_gemm: M in [1,32]");
-  TORCH_CHECK(a.size(1) == K, "K mismatch");
-  TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "K%256==0, N%16==0");
-  TORCH_CHECK(wf.numel() == (long long)N * K, "wf size");
-  auto out = torch::empty({M, (long long)N}, a.options());
-  qsa_skinny_gemm_launch(u16(a), u16(wf), u16m(out), M, (int)N, K,
-                         a.stride(0), cur_stream());
+  auto out = skinny_out(a, N, K, 1, 32, "skinny_gemm");
+  chk_bf16_stream(wf, N, K);
+  qsa_skinny_gemm_launch(u16(a), u16(wf), u16m(out), (int)a.size(0), (int)N,
+                         K, a.stride(0), cur_stream());
   return out;
 }
 
 torch::Tensor skinny_gemm_probe(torch::Tensor a, torch::Tensor wf, long N,
                                 long K, long waves, long nt, long variant) {
-  CHK_DEV(a); CHK_BF16(a); CHK_BF16(wf); CHK_CONT(wf);
-  const int M = a.size(0);
-  auto out = torch::empty({M, (long long)N}, a.options());
-  qsa_skinny_gemm_probe_launch(u16(a), u16(wf), u16m(out), M, (int)N, K,
-                               a.stride(0), (int)waves, (int)nt,
-                               (int)variant, cur_stream());
+  auto out = skinny_out(a, N, K, 1, 32, "skinny_gemm_probe");
+  chk_bf16_stream(wf, N, K);
+  const int ok = qsa_skinny_gemm_probe_launch(
+      u16(a), u16(wf), u16m(out), (int)a.size(0), (int)N, K, a.stride(0),
+      (int)waves, (int)nt, (int)variant, cur_stream());
+  TORCH_CHECK(ok, "skinny_gemm_probe: (waves, nt, variant) not instantiated");
   return out;
+}
+
+// C[M,N] = a @ (scale[N] * dequant(Q))^T through one fp8 skinny
+// configuration; an error when it is not instantiated.
+static torch::Tensor skinny_fp8_config(torch::Tensor a, torch::Tensor qf,
+                                       torch::Tensor scale, long N, long K,
+                                       long waves, long tiles, long nt,
+                                       long mt, const char* op) {
+  TORCH_CHECK(mt >= 1 && mt <= 4, op, ": mt in [1,4]");
+  auto out = skinny_out(a, N, K, tiles, 16 * mt, op);
+  chk_fp8_stream(qf, scale, N, K);
+  const int ok = qsa_skinny_gemm_fp8_config_launch(
+      u16(a), qf.data_ptr<unsigned char>(), scale.data_ptr<float>(),
+      u16m(out), (int)a.size(0), (int)N, K, a.stride(0), (int)waves,
+      (int)tiles, (int)nt, (int)mt, cur_stream());
+  TORCH_CHECK(ok, op, ": (waves, tiles, nt, mt) not instantiated");
+  return out;
+}
+
+torch::Tensor skinny_gemm_fp8(torch::Tensor a, torch::Tensor qf,
+                              torch::Tensor scale, long N, long K) {
+  auto out = skinny_out(a, N, K, 1, 64, "skinny_gemm_fp8");
+  chk_fp8_stream(qf, scale, N, K);
+  qsa_skinny_gemm_fp8_launch(u16(a), qf.data_ptr<unsigned char>(),
+                             scale.data_ptr<float>(), u16m(out),
+                             (int)a.size(0), (int)N, K, a.stride(0),
+                             cur_stream());
+  return out;
+}
+
+torch::Tensor skinny_gemm_fp8_probe(torch::Tensor a, torch::Tensor qf,
+                                    torch::Tensor scale, long N, long K,
+                                    long waves, long tiles, long nt) {
+  return skinny_fp8_config(a, qf, scale, N, K, waves, tiles, nt, 2,
+                           "skinny_gemm_fp8_probe");
+}
+
+torch::Tensor skinny_gemm_fp8_probe_mt(torch::Tensor a, torch::Tensor qf,
+                                       torch::Tensor scale, long N, long K,
+                                       long waves, long tiles, long mt) {
+  return skinny_fp8_config(a, qf, scale, N, K, waves, tiles, 0, mt,
+                           "skinny_gemm_fp8_probe_mt");
 }
 
 torch::Tensor gemm_fp8_batch(torch::Tensor a, torch::Tensor qf,
                              torch::Tensor scale, long N, long K,
                              long splitk) {
   // C[M,N] = a @ (scale * dequant(Q))^T for decode batches 32 < M <= 256
-  CHK_DEV(a); CHK_BF16(a); CHK_DEV(qf); CHK_CONT(qf);
-  TORCH_CHECK(qf.scalar_type() == torch::kUInt8, "qf must be uint8 (fp8)");
-  TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.is_cuda() &&
-                  scale.is_contiguous() && scale.numel() == N, "scale");
-  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
-  chk_gemm_a_aligned(a, "gemm_fp8_batch");
-  const int M = a.size(0);
-  TORCH_CHECK(M >= 1 && M <= 256, "gemm_fp8_batch: M in [1,256]");
-  TORCH_CHECK(a.size(1) == K, "K mismatch");
+  const int M = chk_gemm_a(a, K, 256, "gemm_fp8_batch");
   TORCH_CHECK(N % 64 == 0, "N % 64 == 0");
   TORCH_CHECK(splitk == 1 || splitk == 2 || splitk == 4, "splitk 1/2/4");
   TORCH_CHECK(K % (64 * splitk) == 0, "K % (64*splitk) == 0");
-  TORCH_CHECK(qf.numel() == (long long)N * K, "qf size");
+  chk_fp8_stream(qf, scale, N, K);
   auto out = torch::empty({(long long)M, (long long)N}, a.options());
   torch::Tensor ws;
   float* wsp = nullptr;
@@ -614,63 +668,6 @@ torch::Tensor hash_probe(torch::Tensor tkeys, torch::Tensor tpay,
                         (const unsigned long long*)tpay.data_ptr<int64_t>(),
                         out.data_ptr<int>(), (int)m,
                         (unsigned int)(cap - 1), min_ts, cur_stream());
-  return out;
-}
-
-torch::Tensor skinny_gemm_fp8(torch::Tensor a, torch::Tensor qf,
-                              torch::Tensor scale, long N, long K) {
-  // C[M,N] = a @ (scale[N] * dequant(Q))^T; Q pre-packed fp8 e4m3 in the
-  // fragment-pair-major stream layout (skinny_gemm_fp8.hip header).
-  CHK_DEV(a); CHK_BF16(a); CHK_DEV(qf); CHK_CONT(qf);
-  TORCH_CHECK(qf.scalar_type() == torch::kUInt8, "qf must be uint8 (fp8)");
-  TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.is_cuda() &&
-                  scale.is_contiguous() && scale.numel() == N,
-              "scale must be f32 [N] on device");
-  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
-  chk_gemm_a_aligned(a, "skinny_gemm_fp8");
-  const int M = a.size(0);
-  TORCH_CHECK(M >= 1 && M <= 64, "skinny_gemm_fp8: M in [1,64]");
-  TORCH_CHECK(a.size(1) == K, "K mismatch");
-  TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "K%256==0, N%16==0");
-  TORCH_CHECK(qf.numel() == (long long)N * K, "qf size");
-  auto out = torch::empty({M, (long long)N}, a.options());
-  qsa_skinny_gemm_fp8_launch(u16(a), qf.data_ptr<unsigned char>(),
-                             scale.data_ptr<float>(), u16m(out), M, (int)N,
-                             K, a.stride(0), cur_stream());
-  return out;
-}
-
-torch::Tensor skinny_gemm_fp8_probe(torch::Tensor a, torch::Tensor qf,
-                                    torch::Tensor scale, long N, long K,
-                                    long waves, long tiles, long nt) {
-  CHK_DEV(a); CHK_BF16(a); CHK_CONT(qf);
-  const int M = a.size(0);
-  auto out = torch::empty({M, (long long)N}, a.options());
-  qsa_skinny_gemm_fp8_probe_launch(u16(a), qf.data_ptr<unsigned char>(),
-                                   scale.data_ptr<float>(), u16m(out), M,
-                                   (int)N, K, a.stride(0), (int)waves,
-                                   (int)tiles, (int)nt, cur_stream());
-  return out;
-}
-
-torch::Tensor skinny_gemm_fp8_probe_mt(torch::Tensor a, torch::Tensor qf,
-                                       torch::Tensor scale, long N, long K,
-                                       long waves, long tiles, long mt) {
-  CHK_DEV(a); CHK_BF16(a); CHK_CONT(qf); CHK_DEV(qf); CHK_DEV(scale);
-  TORCH_CHECK(a.dim() == 2 && a.stride(1) == 1, "a rows must be contiguous");
-  const int M = a.size(0);
-  TORCH_CHECK(mt >= 1 && M >= 1 && M <= 16 * mt, "M in [1, 16*mt]");
-  TORCH_CHECK(a.size(1) == K && K % 256 == 0 && tiles >= 1 &&
-                  N % (16 * tiles) == 0,
-              "K%256==0, N%(16*tiles)==0");
-  TORCH_CHECK(qf.numel() == (long long)N * K && scale.numel() == N,
-              "qf / scale size");
-  auto out = torch::empty({M, (long long)N}, a.options());
-  const int ok = qsa_skinny_gemm_fp8_probe_mt_launch(
-      u16(a), qf.data_ptr<unsigned char>(), scale.data_ptr<float>(),
-      u16m(out), M, (int)N, K, a.stride(0), (int)waves, (int)tiles, (int)mt,
-      cur_stream());
-  TORCH_CHECK(ok, "skinny_gemm_fp8_probe_mt: variant not instantiated");
   return out;
 }
 
@@ -822,6 +819,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp8 ablation probe: waves/tiles/nt sweep");
   m.def("skinny_gemm_fp8_probe_mt", &skinny_gemm_fp8_probe_mt,
         "fp8 skinny GEMM with explicit (waves, tiles, m-tiles) for sweeps");
+  m.def("skinny_fp8_class", [](long n, long k) {
+    return std::string(qsa_skinny_fp8_class((int)n, k));
+  }, "shape class the fp8 skinny launcher gives an [n, k] weight");
   m.def("greedy_sample_step", &greedy_sample_step,
         "fused greedy sampling step: windowed argmax, script override, "
         "history/token/counter update (in place)");

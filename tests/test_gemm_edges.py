@@ -83,8 +83,8 @@ def channel_scales(N):
 
 
 def pack_codes(q8):
-    """[N, K] e4m3 codes -> the fragment-pair-major stream of
-    ops/hip/skinny_gemm_fp8.hip.  Needs only K % 64 == 0, which
+    """[N, K] e4m3 codes -> the fp8 fragment-pair-major stream of
+    ops/hip/gemm_core.h.  Needs only K % 64 == 0, which
     D.pack_weight_fp8 (K % 256 == 0) does not offer; fp8_weight asserts the
     two agree byte for byte wherever both apply."""
     n, k = q8.shape

@@ -202,3 +202,71 @@ def test_skinny_kernels_reject_n_not_multiple_of_16(small):
     qf24 = torch.zeros(24 * K, dtype=torch.uint8, device=DEV)
     with pytest.raises(RuntimeError, match="N%16"):
         fn(a, qf24, torch.ones(24, device=DEV), 24, K)
+
+
+# ---- probes get the production checks and more ------------------------------
+
+def test_probes_reject_before_launch(ext, small):
+    """Every call raises in the host checks; none reaches a launch."""
+    _, a, (qf, s, N, K), _ = small["fp8"]
+    _, a16, (wf, N16, K16), _ = small["bf16"]
+    assert (a.shape[0], N, K) == (32, 64, 256)
+    for probe, cfg in ((ext.skinny_gemm_fp8_probe, (3, 1, 0)),
+                       (ext.skinny_gemm_fp8_probe, (8, 2, 1)),
+                       (ext.skinny_gemm_fp8_probe_mt, (3, 1, 2)),
+                       (ext.skinny_gemm_fp8_probe_mt, (8, 1, 3))):
+        with pytest.raises(RuntimeError, match="not instantiated"):
+            probe(a, qf, s, N, K, *cfg)
+    with pytest.raises(RuntimeError, match="not instantiated"):
+        ext.skinny_gemm_probe(a16, wf, N16, K16, 8, 0, 1)
+    for probe, last in ((ext.skinny_gemm_fp8_probe, 0),
+                        (ext.skinny_gemm_fp8_probe_mt, 2)):
+        with pytest.raises(RuntimeError, match=r"N%\(16\*tiles\)"):
+            probe(a, qf, s, N, K, 8, 8, last)       # 64 % 128 != 0
+        with pytest.raises(RuntimeError, match="must be on the GPU"):
+            probe(a, qf.cpu(), s, N, K, 8, 1, last)
+    a33 = torch.cat([a, a[:1]])
+    with pytest.raises(RuntimeError, match=r"M in \[1,32\]"):
+        ext.skinny_gemm_fp8_probe(a33, qf, s, N, K, 8, 1, 0)
+    with pytest.raises(RuntimeError, match=r"M in \[1,32\]"):
+        ext.skinny_gemm_fp8_probe_mt(a33, qf, s, N, K, 8, 1, 2)
+    with pytest.raises(RuntimeError, match="must be on the GPU"):
+        ext.skinny_gemm_probe(a16, wf.cpu(), N16, K16, 8, 0, 0)
+
+
+# ---- one class function, one loop -------------------------------------------
+
+CLASS_GRID = tuple((N, K)
+                   for N in (6128, 6144, 16368, 16384, 16448, 65408, 65536)
+                   for K in (256, 7936, 8192))
+
+
+def test_skinny_fp8_class_agrees(ext):
+    """The launcher's class function and its CPU-only copy in ops.dispatch,
+    on the case table and across every class boundary.  No launch."""
+    for N, K, cls, _ in E.FP8_SHAPES:
+        assert ext.skinny_fp8_class(N, K) == cls
+    for N, K in tuple(s[:2] for s in E.FP8_SHAPES) + CLASS_GRID:
+        assert ext.skinny_fp8_class(N, K) == D.skinny_fp8_class(N, K), (N, K)
+    assert {D.skinny_fp8_class(N, K) for N, K in CLASS_GRID} == \
+        {"lm_head", "wgu", "qkv", "wo", "wdown"}
+
+
+def test_bf16_and_fp8_skinny_are_one_loop(ext):
+    """fp8 weights with unit scales, and the same weights dequantised to
+    bf16 (exact) on the fragment-major pack: both kernels run 8 waves here
+    (class wo), so they add the same products in the same order and the
+    outputs are bit-equal."""
+    case = E.gauss_case("fp8", 32, 48, 2304)
+    N, K = case.N, case.K
+    assert D.skinny_fp8_class(N, K) == "wo"
+    ones = torch.ones(N)
+    w32 = D.unpack_weight_fp8(case.qf, ones, N, K)
+    w = w32.bfloat16()
+    assert torch.equal(w.float(), w32)
+    wf, qf, s1 = to_dev(D.pack_weight_frag(w)), to_dev(case.qf), to_dev(ones)
+    for M in (1, 17, 32):
+        a = to_dev(case.a[:M].contiguous())
+        E.assert_bits_equal(ext.skinny_gemm_fp8(a, qf, s1, N, K),
+                            ext.skinny_gemm(a, wf, N, K).cpu(),
+                            f"fp8 vs bf16 skinny M={M}")

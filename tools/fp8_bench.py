@@ -59,15 +59,11 @@ def main():
                                       (4, 4, 0), (4, 8, 0), (2, 8, 0)]:
                 if N % (16 * tiles):
                     continue
-                try:
-                    t = timeit(lambda: ext().skinny_gemm_fp8_probe(
-                        a, qf, s, N, K, waves, tiles, ntl), reps=20)
-                    print(f"    probe {name} w{waves} t{tiles} nt{ntl}: "
-                          f"{t:.1f} us ({(N*K)/(t*1e-6)/1e9:.0f} GB/s)",
-                          file=sys.stderr)
-                except Exception as e:
-                    print(f"    probe {name} w{waves} t{tiles}: {e}",
-                          file=sys.stderr)
+                t = timeit(lambda: ext().skinny_gemm_fp8_probe(
+                    a, qf, s, N, K, waves, tiles, ntl), reps=20)
+                print(f"    probe {name} w{waves} t{tiles} nt{ntl}: "
+                      f"{t:.1f} us ({(N*K)/(t*1e-6)/1e9:.0f} GB/s)",
+                      file=sys.stderr)
         # correctness spot check
         ref = a.float() @ D.unpack_weight_fp8(qf, s, N, K).T
         out = ext().skinny_gemm_fp8(a, qf, s, N, K).float()
