@@ -15,6 +15,7 @@ n_experts/ep_size full experts.
 
 from __future__ import annotations
 
+import os
 from dataclasses import dataclass
 
 import torch
@@ -69,6 +70,11 @@ class MixtralModel(LlamaModel):
         assert cfg.n_experts % ep_size == 0, "experts must divide EP"
         self.ep_size = ep_size
         self._dispatch = None  # built after super().__init__ sets tp_rank
+        # routed decode FFN (ops/hip/moe.hip), both knobs read once here:
+        # QSA_MOE_ROUTED=0 keeps the dense loop, QSA_FP8=0 the bf16 stream
+        self._moe_routed = os.environ.get("QSA_MOE_ROUTED", "1") != "0"
+        self._moe_fp8 = os.environ.get("QSA_FP8", "1") == "1"
+        self._row_live = None  # [B] i32 during forward_decode, else None
         super().__init__(cfg, device=device, dtype=dtype, seed=seed,
                          tp_rank=tp_rank, tp_size=tp_size, tp_group=tp_group)
         self._dispatch = ExpertDispatch(cfg.n_experts, ep_size,
@@ -99,8 +105,58 @@ class MixtralModel(LlamaModel):
                                  D.pack_weight_frag(wdown))
             else:
                 del wgu, wdown
-        return {"router": router, "experts": experts,
-                "experts_f": packed}
+        out = {"router": router, "experts": experts, "experts_f": packed}
+        # stacked [E, ...] weight streams of the routed decode path: every
+        # expert in one stream per projection, no size limit (the grouped
+        # kernels read only the experts that rows chose)
+        if pack and self._moe_routed and self.ep_size == 1 and \
+                D.can_pack_weight(2 * c.ffn, c.hidden) and \
+                D.can_pack_weight(c.hidden, c.ffn):
+            order = range(c.n_experts)
+            out["moe_wgu"] = D.moe_pack_experts(
+                [experts[e][0] for e in order], self._moe_fp8)
+            out["moe_wdown"] = D.moe_pack_experts(
+                [experts[e][1] for e in order], self._moe_fp8)
+        return out
+
+    @torch.no_grad()
+    def forward_decode(self, tokens, kv, block_table, seq_lens, positions):
+        """The Llama decode step; while it runs, _ffn knows which rows are
+        live.  The engine leaves graph-padding rows at seq_lens == 0, so a
+        padded rung streams only the experts its live rows chose (the
+        padding rows' FFN output is zero; nothing reads those rows)."""
+        if self._moe_routed and seq_lens.is_cuda:
+            self._row_live = (seq_lens > 0).to(torch.int32)
+        try:
+            return super().forward_decode(tokens, kv, block_table, seq_lens,
+                                          positions)
+        finally:
+            self._row_live = None
+
+    def _ffn_routed(self, L: dict, h: torch.Tensor, top_idx: torch.Tensor,
+                    top_w: torch.Tensor) -> torch.Tensor:
+        """Five launches, no host sync: dispatch -> grouped GEMM -> SwiGLU
+        -> grouped GEMM -> combine, on the experts that live rows chose.
+        In bf16 bit-identical to the dense loop below (ARCHITECTURE.md,
+        "Routed MoE decode")."""
+        c = self._moe_cfg
+        live = self._row_live
+        if live is not None and live.numel() != h.shape[0]:
+            live = None
+        counts, slot, xg = D.moe_dispatch(h, top_idx, c.n_experts, live)
+        if self._moe_fp8:
+            gu = D.moe_skinny_linear_fp8(xg, counts, *L["moe_wgu"],
+                                         2 * c.ffn, c.hidden)
+            act = D.moe_swiglu(gu, counts)
+            y = D.moe_skinny_linear_fp8(act, counts, *L["moe_wdown"],
+                                        c.hidden, c.ffn)
+        else:
+            gu = D.moe_skinny_linear(xg, counts, L["moe_wgu"], 2 * c.ffn,
+                                     c.hidden)
+            act = D.moe_swiglu(gu, counts)
+            y = D.moe_skinny_linear(act, counts, L["moe_wdown"], c.hidden,
+                                    c.ffn)
+        return D.moe_combine(y, slot, top_idx, top_w)
 
     def _ffn(self, L: dict, h: torch.Tensor) -> torch.Tensor:
         c = self._moe_cfg
@@ -121,6 +177,9 @@ class MixtralModel(LlamaModel):
             return F.linear(act, wdown)
 
         if self.ep_size == 1:
+            if self._moe_routed and h.is_cuda and "moe_wgu" in L and \
+                    1 <= h.shape[0] <= D.MOE_MAX_ROWS:
+                return self._ffn_routed(L, h, top_idx, top_w)
             if h.shape[0] <= 64 and h.is_cuda:
                 # decode-sized batch: dense compute-all-experts.  Top-2/8 on
                 # 24+ tokens touches every expert's weights anyway (the MoE

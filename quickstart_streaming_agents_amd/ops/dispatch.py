@@ -291,6 +291,130 @@ def skinny_fp8_row_limit(n: int, k: int) -> int:
     return 64 if skinny_fp8_class(n, k) in SKINNY_FP8_WIDE_CLASSES else 32
 
 
+# ---- routed MoE decode FFN (ops/hip/moe.hip) ------------------------------
+# T <= 64 rows, E <= 16 experts, top-k <= 4.  cap, the row capacity per
+# expert, is 32 at T <= 32, else 64.  The GPU kernels leave rows at or past
+# counts[e] of every [E, cap, ...] buffer unwritten; the CPU references
+# leave them zero.
+
+MOE_MAX_ROWS = 64
+
+
+def moe_cap(t: int) -> int:
+    return 32 if t <= 32 else 64
+
+
+def moe_pack_experts(ws: list[torch.Tensor], fp8: bool):
+    """Stack the experts' [N, K] weights into one stream per layer:
+    fp8 -> (qf [E, ...] uint8, scale [E, N] f32) of pack_weight_fp8,
+    else wf [E, ...] bf16 of pack_weight_frag."""
+    if fp8:
+        packed = [pack_weight_fp8(w) for w in ws]
+        return (torch.stack([p[0] for p in packed]).contiguous(),
+                torch.stack([p[1] for p in packed]).contiguous())
+    return torch.stack([pack_weight_frag(w) for w in ws]).contiguous()
+
+
+def moe_dispatch(h: torch.Tensor, top_idx: torch.Tensor, n_experts: int,
+                 row_live: torch.Tensor | None = None):
+    """Routing + gather: h [T, H], top_idx [T, k] i64, row_live [T] i32 or
+    None -> (counts [E] i32, slot [T, k] i32, xg [E, cap, H]).
+
+    xg[e, slot[t, j]] = h[t] for every live row t and pick j with
+    top_idx[t, j] = e; slots ascend with the row index inside an expert;
+    a dead row (row_live == 0), or a pick outside [0, E), has slot -1.
+    Precondition: a row's k experts are distinct."""
+    if h.is_cuda:
+        return tuple(ext().moe_dispatch(h, top_idx, n_experts, row_live))
+    T, H = h.shape
+    k = top_idx.shape[1]
+    assert 1 <= T <= MOE_MAX_ROWS and 1 <= k <= 4 and 1 <= n_experts <= 16
+    cap = moe_cap(T)
+    counts = torch.zeros(n_experts, dtype=torch.int32)
+    slot = torch.full((T, k), -1, dtype=torch.int32)
+    xg = torch.zeros(n_experts, cap, H, dtype=h.dtype)
+    live = [True] * T if row_live is None else \
+        [bool(v) for v in row_live.tolist()]
+    idx = top_idx.tolist()
+    for t in range(T):
+        if not live[t]:
+            continue
+        for e in sorted(set(idx[t])):
+            if not 0 <= e < n_experts:
+                continue
+            s = int(counts[e])
+            for j in range(k):
+                if idx[t][j] == e:
+                    slot[t, j] = s
+            xg[e, s] = h[t]
+            counts[e] = s + 1
+    return counts, slot, xg
+
+
+def _moe_grouped(xg, counts, n, fn):
+    out = torch.zeros(xg.shape[0], xg.shape[1], n, dtype=xg.dtype,
+                      device=xg.device)
+    for e, c in enumerate(counts.tolist()):
+        if c > 0:
+            out[e, :c] = fn(e, xg[e, :c])
+    return out
+
+
+def moe_skinny_linear(xg: torch.Tensor, counts: torch.Tensor,
+                      wf: torch.Tensor, n: int, k: int) -> torch.Tensor:
+    """Grouped skinny_linear: out[e, :counts[e]] = xg[e, :counts[e]] @
+    W_e^T on the stacked bf16 stream; experts with no rows are not read.
+    Each live row has the bits skinny_linear gives it."""
+    if xg.is_cuda:
+        return ext().moe_skinny_gemm(xg, counts, wf, n, k)
+    return _moe_grouped(xg, counts, n,
+                        lambda e, x: skinny_linear(x, wf[e], n, k))
+
+
+def moe_skinny_linear_fp8(xg: torch.Tensor, counts: torch.Tensor,
+                          qf: torch.Tensor, scale: torch.Tensor, n: int,
+                          k: int) -> torch.Tensor:
+    """Grouped skinny_linear_fp8 on the stacked fp8 stream and [E, N]
+    scales; experts with no rows are not read."""
+    if xg.is_cuda:
+        return ext().moe_skinny_gemm_fp8(xg, counts, qf, scale, n, k)
+    return _moe_grouped(
+        xg, counts, n,
+        lambda e, x: skinny_linear_fp8(x, qf[e], scale[e], n, k))
+
+
+def moe_swiglu(gu: torch.Tensor, counts: torch.Tensor) -> torch.Tensor:
+    """act[e, r] = silu(gu[e, r, :F]) * gu[e, r, F:] for r < counts[e]."""
+    if gu.is_cuda:
+        return ext().moe_swiglu(gu, counts)
+    f = gu.shape[2] // 2
+    return _moe_grouped(gu, counts, f,
+                        lambda e, g: swiglu(g[:, :f], g[:, f:]))
+
+
+def moe_combine(y: torch.Tensor, slot: torch.Tensor, top_idx: torch.Tensor,
+                top_w: torch.Tensor) -> torch.Tensor:
+    """out[t] = sum over row t's picks of top_w[t, j] * y[e, slot[t, j]],
+    in ascending expert index, in f32 from zero with the multiply and the
+    add rounded separately (no FMA), rounded once to y's dtype: the
+    arithmetic of the dense masked sum over all experts.  Dead picks
+    (slot < 0) add nothing, so a dead row gives zeros."""
+    if y.is_cuda:
+        return ext().moe_combine(y, slot, top_idx, top_w)
+    T, k = top_idx.shape
+    out = torch.zeros(T, y.shape[2], dtype=torch.float32)
+    for e in range(y.shape[0]):
+        for j in range(k):
+            rows = ((top_idx[:, j] == e) & (slot[:, j] >= 0)) \
+                .nonzero(as_tuple=True)[0]
+            if rows.numel() == 0:
+                continue
+            prod = top_w[rows, j].float().unsqueeze(1) * \
+                y[e, slot[rows, j].long()].float()
+            out[rows] = out[rows] + prod
+    return out.to(y.dtype)
+
+
 # ---- fused greedy sampling step ------------------------------------------
 
 def greedy_sample_step(logits: torch.Tensor, lo: int, hi: int, eos: int,

@@ -35,6 +35,25 @@ __device__ __forceinline__ unsigned int f32x2_to_bf16x2(float a, float b) {
   return (unsigned int)f32_to_bf16(a) | ((unsigned int)f32_to_bf16(b) << 16);
 }
 
+// ---- SwiGLU on 8 bf16: silu(gate) * up, f32 inside, one rounding ----------
+// The one definition of the element arithmetic, shared by the flat kernel
+// (elementwise.hip) and the routed-MoE one (moe.hip).
+__device__ __forceinline__ uint4 qsa_swiglu8(uint4 g, uint4 u) {
+  unsigned int gp[4] = {g.x, g.y, g.z, g.w};
+  unsigned int upk[4] = {u.x, u.y, u.z, u.w};
+  uint4 outv;
+  unsigned int* po = &outv.x;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    float2 a = bf16x2_to_f32x2(gp[j]);
+    float2 b = bf16x2_to_f32x2(upk[j]);
+    float s0 = a.x / (1.f + __expf(-a.x));
+    float s1 = a.y / (1.f + __expf(-a.y));
+    po[j] = f32x2_to_bf16x2(s0 * b.x, s1 * b.y);
+  }
+  return outv;
+}
+
 // ---- wave reductions (64-lane) --------------------------------------------
 __device__ __forceinline__ float wave_reduce_sum(float v) {
 #pragma unroll

@@ -152,19 +152,7 @@ qsa_swiglu_kernel(const unsigned short* __restrict__ gate,
     const long long off = r * in_stride + cidx;
     uint4 g = *reinterpret_cast<const uint4*>(gate + off);
     uint4 u = *reinterpret_cast<const uint4*>(up + off);
-    unsigned int gp[4] = {g.x, g.y, g.z, g.w};
-    unsigned int upk[4] = {u.x, u.y, u.z, u.w};
-    uint4 outv;
-    unsigned int* po = &outv.x;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float2 a = bf16x2_to_f32x2(gp[j]);
-      float2 b = bf16x2_to_f32x2(upk[j]);
-      float s0 = a.x / (1.f + __expf(-a.x));
-      float s1 = a.y / (1.f + __expf(-a.y));
-      po[j] = f32x2_to_bf16x2(s0 * b.x, s1 * b.y);
-    }
-    *reinterpret_cast<uint4*>(y + i) = outv;
+    *reinterpret_cast<uint4*>(y + i) = qsa_swiglu8(g, u);
   }
 }
 

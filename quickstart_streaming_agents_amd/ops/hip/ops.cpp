@@ -93,6 +93,23 @@ extern "C" int qsa_skinny_gemm_fp8_config_launch(
     unsigned short*, int, int, long long, long long, int, int, int, int,
     hipStream_t);
 extern "C" const char* qsa_skinny_fp8_class(int, long long);
+extern "C" void qsa_moe_dispatch_launch(const unsigned short*,
+                                        const long long*, const int*, int*,
+                                        int*, unsigned short*, int, int, int,
+                                        int, int, hipStream_t);
+extern "C" void qsa_moe_skinny_gemm_bf16_launch(
+    const unsigned short*, const unsigned short*, unsigned short*, const int*,
+    int, int, int, long long, hipStream_t);
+extern "C" int qsa_moe_skinny_gemm_fp8_launch(
+    const unsigned short*, const unsigned char*, const float*,
+    unsigned short*, const int*, int, int, int, long long, hipStream_t);
+extern "C" void qsa_moe_swiglu_launch(const unsigned short*, unsigned short*,
+                                      const int*, int, int, long long,
+                                      hipStream_t);
+extern "C" void qsa_moe_combine_launch(const unsigned short*, const int*,
+                                       const long long*, const float*,
+                                       unsigned short*, int, int, int, int,
+                                       int, hipStream_t);
 extern "C" void qsa_greedy_sample_launch(
     const unsigned short*, int, long long, int, int, int, const long long*,
     const unsigned char*, int, long long*, long long*, long long, int,
@@ -631,6 +648,159 @@ torch::Tensor gemm_fp8_batch(torch::Tensor a, torch::Tensor qf,
   return out;
 }
 
+// ---- routed MoE decode FFN (moe.hip) ----------------------------------------
+// Limits: T <= 64 rows, E <= 16 experts, top-k <= 4; cap (rows per expert)
+// is 32 at T <= 32, else 64.
+
+static bool aligned16(const torch::Tensor& t) {
+  return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
+}
+
+// counts [E] i32 on the device; returns E.
+static int chk_moe_counts(const torch::Tensor& counts, long E) {
+  CHK_DEV(counts); CHK_I32(counts); CHK_CONT(counts);
+  TORCH_CHECK(counts.dim() == 1 && counts.numel() == E, "counts must be [E]");
+  TORCH_CHECK(E >= 1 && E <= 16, "moe: E in [1,16]");
+  return (int)E;
+}
+
+// A grouped activation buffer [E, cap, cols] bf16, cap 32 or 64.
+static void chk_moe_rows(const torch::Tensor& x, const char* name) {
+  CHK_DEV(x); CHK_BF16(x); CHK_CONT(x);
+  TORCH_CHECK(x.dim() == 3, name, " must be [E, cap, cols]");
+  TORCH_CHECK(x.size(1) == 32 || x.size(1) == 64, name, ": cap must be 32/64");
+  TORCH_CHECK(x.size(2) % 8 == 0 && aligned16(x), name,
+              " rows must be 16-byte aligned");
+}
+
+// top_idx [T,k] i64 (as torch.topk returns it), T <= 64, k <= 4.
+static void chk_moe_top_idx(const torch::Tensor& top_idx, long T) {
+  CHK_DEV(top_idx); CHK_CONT(top_idx);
+  TORCH_CHECK(top_idx.scalar_type() == at::kLong && top_idx.dim() == 2 &&
+                  top_idx.size(0) == T, "top_idx must be i64 [T, k]");
+  TORCH_CHECK(T >= 1 && T <= 64, "moe: T in [1,64]");
+  TORCH_CHECK(top_idx.size(1) >= 1 && top_idx.size(1) <= 4,
+              "moe: top-k in [1,4]");
+}
+
+// h [T,H] -> (counts [E], slot [T,k], xg [E,cap,H]): slot is the row's slot
+// inside its expert, ascending by row index, -1 for a dead row.  Rows of xg
+// at or past counts[e] are left unwritten.  A row's k experts must be
+// distinct (not checked).
+std::vector<torch::Tensor> moe_dispatch(torch::Tensor h, torch::Tensor top_idx,
+                                        long n_experts,
+                                        c10::optional<torch::Tensor> row_live) {
+  CHK_DEV(h); CHK_BF16(h); CHK_CONT(h);
+  TORCH_CHECK(h.dim() == 2, "h must be [T, H]");
+  const long T = h.size(0), H = h.size(1);
+  chk_moe_top_idx(top_idx, T);
+  TORCH_CHECK(n_experts >= 1 && n_experts <= 16, "moe: E in [1,16]");
+  TORCH_CHECK(H % 8 == 0 && aligned16(h), "h rows must be 16-byte aligned");
+  const int k = top_idx.size(1);
+  const int* live = nullptr;
+  if (row_live.has_value()) {
+    const auto& rl = row_live.value();
+    CHK_DEV(rl); CHK_I32(rl); CHK_CONT(rl);
+    TORCH_CHECK(rl.numel() == T, "row_live must be [T]");
+    live = rl.data_ptr<int>();
+  }
+  const long cap = T <= 32 ? 32 : 64;
+  auto opts_i = h.options().dtype(at::kInt);
+  auto counts = torch::empty({n_experts}, opts_i);
+  auto slot = torch::empty({T, (long)k}, opts_i);
+  auto xg = torch::empty({n_experts, cap, H}, h.options());
+  qsa_moe_dispatch_launch(
+      u16(h), reinterpret_cast<const long long*>(top_idx.data_ptr<int64_t>()),
+      live, counts.data_ptr<int>(), slot.data_ptr<int>(), u16m(xg), (int)T,
+      (int)H, (int)n_experts, k, (int)cap, cur_stream());
+  return {counts, slot, xg};
+}
+
+// out[e, :counts[e]] = xg[e, :counts[e]] @ W_e^T on the stacked bf16 fragment
+// stream wf [E, ...]; experts with no rows are not read.  Rows at or past
+// counts[e] of the [E, cap, N] result are left unwritten.
+torch::Tensor moe_skinny_gemm(torch::Tensor xg, torch::Tensor counts,
+                              torch::Tensor wf, long N, long K) {
+  chk_moe_rows(xg, "xg");
+  const int E = chk_moe_counts(counts, xg.size(0));
+  TORCH_CHECK(xg.size(2) == K, "K mismatch");
+  TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "K%256==0, N%16==0");
+  CHK_DEV(wf); CHK_BF16(wf); CHK_CONT(wf);
+  TORCH_CHECK(wf.size(0) == E && wf.numel() == (long long)E * N * K,
+              "wf must be the [E, ...] stack of N*K streams");
+  auto out = torch::empty({(long)E, xg.size(1), N}, xg.options());
+  qsa_moe_skinny_gemm_bf16_launch(u16(xg), u16(wf), u16m(out),
+                                  counts.data_ptr<int>(), E, (int)xg.size(1),
+                                  (int)N, K, cur_stream());
+  return out;
+}
+
+torch::Tensor moe_skinny_gemm_fp8(torch::Tensor xg, torch::Tensor counts,
+                                  torch::Tensor qf, torch::Tensor scale,
+                                  long N, long K) {
+  chk_moe_rows(xg, "xg");
+  const int E = chk_moe_counts(counts, xg.size(0));
+  TORCH_CHECK(xg.size(2) == K, "K mismatch");
+  TORCH_CHECK(K % 256 == 0 && N % 16 == 0, "K%256==0, N%16==0");
+  CHK_DEV(qf); CHK_CONT(qf);
+  TORCH_CHECK(qf.scalar_type() == torch::kUInt8, "qf must be uint8 (fp8)");
+  TORCH_CHECK(qf.size(0) == E && qf.numel() == (long long)E * N * K,
+              "qf must be the [E, ...] stack of N*K streams");
+  TORCH_CHECK(scale.scalar_type() == torch::kFloat32 && scale.is_cuda() &&
+                  scale.is_contiguous() && scale.dim() == 2 &&
+                  scale.size(0) == E && scale.size(1) == N,
+              "scale must be f32 [E, N] on device");
+  // the launcher's tiles (4 wgu, 2 qkv, else 1) divide N/16 by the class rule
+  const std::string cls = qsa_skinny_fp8_class((int)N, K);
+  const long tiles = cls == "wgu" ? 4 : cls == "qkv" ? 2 : 1;
+  TORCH_CHECK(N % (16 * tiles) == 0, "N%(16*tiles)==0");
+  auto out = torch::empty({(long)E, xg.size(1), N}, xg.options());
+  const int ok = qsa_moe_skinny_gemm_fp8_launch(
+      u16(xg), qf.data_ptr<unsigned char>(), scale.data_ptr<float>(),
+      u16m(out), counts.data_ptr<int>(), E, (int)xg.size(1), (int)N, K,
+      cur_stream());
+  TORCH_CHECK(ok, "moe_skinny_gemm_fp8: the lm_head shape class (N >= 65536) "
+              "is not supported");
+  return out;
+}
+
+// act[e, r, :] = silu(gu[e, r, :F]) * gu[e, r, F:] for r < counts[e].
+torch::Tensor moe_swiglu(torch::Tensor gu, torch::Tensor counts) {
+  chk_moe_rows(gu, "gu");
+  const int E = chk_moe_counts(counts, gu.size(0));
+  TORCH_CHECK(gu.size(2) % 16 == 0, "gu cols (2F) % 16 == 0");
+  const long F = gu.size(2) / 2;
+  auto act = torch::empty({(long)E, gu.size(1), F}, gu.options());
+  qsa_moe_swiglu_launch(u16(gu), u16m(act), counts.data_ptr<int>(), E,
+                        (int)gu.size(1), F, cur_stream());
+  return act;
+}
+
+// out[t, :] = sum over row t's picks of top_w * y[top_idx, slot], ascending
+// expert index, f32 with separately rounded multiply and add, one rounding
+// to bf16.  Dead rows give zeros.
+torch::Tensor moe_combine(torch::Tensor y, torch::Tensor slot,
+                          torch::Tensor top_idx, torch::Tensor top_w) {
+  chk_moe_rows(y, "y");
+  const long E = y.size(0), H = y.size(2);
+  TORCH_CHECK(E >= 1 && E <= 16, "moe: E in [1,16]");
+  const long T = slot.size(0);
+  chk_moe_top_idx(top_idx, T);
+  CHK_DEV(slot); CHK_I32(slot); CHK_CONT(slot);
+  CHK_DEV(top_w); CHK_F32(top_w); CHK_CONT(top_w);
+  TORCH_CHECK(slot.sizes() == top_idx.sizes() &&
+                  top_w.sizes() == top_idx.sizes(),
+              "slot, top_idx and top_w must all be [T, k]");
+  TORCH_CHECK(y.size(1) == (T <= 32 ? 32 : 64), "y cap does not match T");
+  auto out = torch::empty({T, H}, y.options());
+  qsa_moe_combine_launch(
+      u16(y), slot.data_ptr<int>(),
+      reinterpret_cast<const long long*>(top_idx.data_ptr<int64_t>()),
+      top_w.data_ptr<float>(), u16m(out), (int)T, (int)H, (int)E,
+      (int)top_idx.size(1), (int)y.size(1), cur_stream());
+  return out;
+}
+
 std::vector<torch::Tensor> hash_build(torch::Tensor keys,
                                       torch::Tensor ts) {
   // latest-event-time-per-key hash table in HBM (K8 streaming join state)
@@ -822,6 +992,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("skinny_fp8_class", [](long n, long k) {
     return std::string(qsa_skinny_fp8_class((int)n, k));
   }, "shape class the fp8 skinny launcher gives an [n, k] weight");
+  m.def("moe_dispatch", &moe_dispatch,
+        "routed MoE: per-expert counts, row slots and gathered rows",
+        py::arg("h"), py::arg("top_idx"), py::arg("n_experts"),
+        py::arg("row_live") = py::none());
+  m.def("moe_skinny_gemm", &moe_skinny_gemm,
+        "grouped skinny GEMM over routed experts (bf16 stream)");
+  m.def("moe_skinny_gemm_fp8", &moe_skinny_gemm_fp8,
+        "grouped skinny GEMM over routed experts (fp8 stream)");
+  m.def("moe_swiglu", &moe_swiglu, "SwiGLU over the live rows of each expert");
+  m.def("moe_combine", &moe_combine,
+        "gate-weighted sum of a row's expert outputs (f32, no FMA)");
   m.def("greedy_sample_step", &greedy_sample_step,
         "fused greedy sampling step: windowed argmax, script override, "
         "history/token/counter update (in place)");

@@ -25,6 +25,7 @@ sources = [
     os.path.join(HIP_DIR, "paged_attn.hip"),
     os.path.join(HIP_DIR, "skinny_gemm.hip"),
     os.path.join(HIP_DIR, "skinny_gemm_fp8.hip"),
+    os.path.join(HIP_DIR, "moe.hip"),
     os.path.join(HIP_DIR, "hash_join.hip"),
     os.path.join(HIP_DIR, "gemm_fp8_batch.hip"),
     os.path.join(HIP_DIR, "topk_cosine.hip"),
