@@ -22,17 +22,64 @@ so a nearly drained batch pays for its own rows, not for max_batch
 
 Sampling: free text decodes greedily (deterministic); grammar decision
 tokens sample from the model's masked distribution under a fixed seed
-(models/grammar.py) — the whole benchmark stays reproducible.
+(models/grammar.py) — the whole benchmark stays reproducible.  A request
+may carry its own SamplingParams (temperature, top-k, top-p, seed): its
+tokens are drawn by the seeded rule of ops/dispatch.py (sample_step), a
+function of the row's logits, parameters, seed and absolute position alone,
+so they do not depend on batch mates, ladder rung, run length or TP rank.
 """
 
 from __future__ import annotations
 
+import math
+import random
 import time
 from dataclasses import dataclass, field
 
 import torch
 
 from .llama import LlamaModel
+
+
+@dataclass(frozen=True)
+class SamplingParams:
+    """Per-request sampling.  temperature 0 is greedy; top_k 0 and top_p 1
+    are off; seed None draws one from the engine's seed generator."""
+    temperature: float = 0.0
+    top_k: int = 0
+    top_p: float = 1.0
+    seed: int | None = None
+
+    def __post_init__(self):
+        t = self.temperature
+        if not (isinstance(t, (int, float)) and math.isfinite(t) and t >= 0):
+            raise ValueError(f"temperature must be finite and >= 0, got {t!r}")
+        if not math.isfinite(self.inv_temp):
+            raise ValueError(f"temperature {t!r} is too small for f32")
+        if not (isinstance(self.top_k, int) and 0 <= self.top_k < 2 ** 31):
+            raise ValueError(f"top_k must be an int >= 0, got {self.top_k!r}")
+        if not 0.0 < self.top_p <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {self.top_p!r}")
+        if self.seed is not None and not 0 <= self.seed < 2 ** 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {self.seed!r}")
+
+    @property
+    def inv_temp(self) -> float:
+        """float32(1 / temperature), 0 for greedy."""
+        if self.temperature == 0:
+            return 0.0
+        return float(torch.tensor(1.0 / self.temperature,
+                                  dtype=torch.float64).float())
+
+    @property
+    def top_p_q(self) -> int:
+        """top_p in 16-bit fixed point, 65536 = off."""
+        return min(65536, max(1, int(self.top_p * 65536 + 0.5)))
+
+
+def _seed_i64(seed: int) -> int:
+    """The 64 seed bits as the two's-complement value an i64 tensor holds."""
+    return seed - (1 << 64) if seed >= 1 << 63 else seed
 
 
 @dataclass
@@ -51,6 +98,15 @@ class Sequence:
     decision_allowed: list[int] | None = None
     branches: dict[int, list[int]] | None = None
     script: list[int] | None = None
+    # per-request sampling (None: the engine-wide policy) and the seed its
+    # draws actually use
+    sampling: SamplingParams | None = None
+    seed: int | None = None
+
+    @property
+    def sampled(self) -> bool:
+        """Draws at a temperature of its own above 0."""
+        return self.sampling is not None and self.sampling.temperature > 0
 
 
 @dataclass
@@ -69,6 +125,10 @@ class EngineStats:
     # replays bucketed by the ladder rung that ran them
     decode_steps_by_live: dict = field(default_factory=dict)
     decode_steps_by_rung: dict = field(default_factory=dict)
+    # decode steps by sampler: graph replays by the ladder that ran them,
+    # eager steps "sampled" when a live row has a temperature of its own > 0
+    decode_steps_by_sampler: dict = field(
+        default_factory=lambda: {"greedy": 0, "sampled": 0})
 
 
 import os as _os
@@ -127,10 +187,12 @@ class Engine:
                  eos_id: int | None = None, prefill_batch_tokens: int = 65536,
                  temperature: float = 0.0,
                  valid_vocab: tuple[int, int] | None = None,
-                 decision_temperature: float = 1.0):
+                 decision_temperature: float = 1.0, seed: int = 0):
         if torch.cuda.is_available():
             _enable_tunableop()   # load the pre-tuned GEMM picks
         self.model = model
+        # seeds of requests whose SamplingParams leave the seed open
+        self._seed_rng = random.Random(seed)
         # temperature 0 = greedy (the deterministic benchmark contract);
         # > 0 samples via the Gumbel-argmax trick, which stays a single
         # argmax and is hipGraph-capture-safe (torch captures RNG state
@@ -167,6 +229,8 @@ class Engine:
         # on a given stack the engine falls back to eager decode.
         # TP NOTE: grammar decision sampling draws torch.rand — TP ranks
         # must share a seed so sampled decisions agree across the group.
+        # Rows that have `sampling` need no shared torch seed: their draws
+        # are a function of the logits, the request's seed and the position.
         # Only a model that lives on the GPU is captured: capturing a CPU
         # model on a GPU host records an empty graph whose replays emit
         # nothing (every decoded token reads back as 0).
@@ -177,6 +241,11 @@ class Engine:
         self._rungs: tuple = ()
         self._graph_failed = False
         self._gbuf: dict = {}
+        # the second ladder (per-request sampler), captured on first need
+        self._graphs_sampled: dict = {}
+        self._sampled_failed = False
+        self._graph_pool = None
+        self._graph_body = None
         # free-text sampling mask: tokens outside [lo, hi) (plus EOS) are
         # never emitted — keeps random-init decode inside the tokenizer's
         # trained vocab so outputs are real text (models/grammar.py)
@@ -204,8 +273,49 @@ class Engine:
         return torch.argmax(logits.float() + self.temperature * gumbel,
                             dim=-1)
 
+    def _window(self, logits: torch.Tensor) -> tuple[int, int, int]:
+        """lo, hi, eos of the samplers: the valid-vocab window, or the
+        whole vocabulary without one."""
+        lo, hi = self._valid_vocab or (0, logits.shape[-1])
+        return lo, hi, -1 if self.eos_id is None else int(self.eos_id)
+
+    def _sample_rows(self, logits: torch.Tensor, seqs: list["Sequence"],
+                     pos: list[int]) -> list[int]:
+        """Tokens of rows that have `sampling`: the seeded draw of
+        ops/dispatch.py at absolute position pos[i] (row i of logits)."""
+        from ..ops import dispatch as D
+        dev = logits.device
+
+        def col(vals, dtype):
+            return torch.tensor(vals, dtype=dtype, device=dev)
+
+        lo, hi, eos = self._window(logits)
+        toks = D.sample_tokens(
+            logits.to(torch.bfloat16).contiguous(), lo, hi, eos,
+            col([s.sampling.inv_temp for s in seqs], torch.float32),
+            col([s.sampling.top_k for s in seqs], torch.int32),
+            col([s.sampling.top_p_q for s in seqs], torch.int32),
+            col([_seed_i64(s.seed) for s in seqs], torch.int64),
+            col(pos, torch.int32))
+        return [int(t) for t in toks.tolist()]
+
     def _sample_first(self, logits: torch.Tensor,
                       admitted: list["Sequence"]) -> list[int]:
+        """Each admitted sequence's first token.  Rows that have `sampling`
+        and no decision mask draw theirs at position len(prompt); the rest
+        follow the engine-wide policy, untouched by those rows."""
+        out = self._sample_first_policy(logits, admitted)
+        own = [i for i, s in enumerate(admitted)
+               if s.sampling is not None and not s.decision_allowed]
+        if own:
+            toks = self._sample_rows(logits[own], [admitted[i] for i in own],
+                                     [len(admitted[i].prompt) for i in own])
+            for i, t in zip(own, toks):
+                out[i] = t
+        return out
+
+    def _sample_first_policy(self, logits: torch.Tensor,
+                             admitted: list["Sequence"]) -> list[int]:
         """Sample each admitted sequence's first token, honoring per-row
         decision masks (grammar turns) with ONE host sync."""
         free = self._sample(logits)
@@ -284,10 +394,16 @@ class Engine:
                                        device=dev),
             # scratch of the fused sampler kernel
             "ticket": torch.zeros(1, dtype=torch.int32, device=dev),
+            # per-request sampling parameters (inv_temp 0: a greedy row)
+            "inv_temp": torch.zeros(B, dtype=torch.float32, device=dev),
+            "top_k": torch.zeros(B, dtype=torch.int32, device=dev),
+            "top_p_q": torch.full((B,), 65536, dtype=torch.int32,
+                                  device=dev),
+            "seed": torch.zeros(B, dtype=torch.int64, device=dev),
         }
         eos = -1 if self.eos_id is None else int(self.eos_id)
 
-        def body(b: int):
+        def body(b: int, sampled: bool = False):
             # self-feeding decode step on rows [0, b): advance seq_lens
             # in-graph, append the step's k/v at seq_lens-1, attend, sample,
             # record, feed back.  forward_decode derives positions from
@@ -296,6 +412,18 @@ class Engine:
             seq_lens.add_(gb["active"][:b])
             logits = self.model.forward_decode(
                 tokens, self.kv, gb["block_table"][:b], seq_lens, None)
+            if sampled:
+                # the second ladder: every row through the per-request
+                # sampler, drawn at its absolute position (seq_lens after
+                # the add_)
+                lo, hi, _ = self._window(logits)
+                D.sample_step(
+                    logits.to(torch.bfloat16), lo, hi, eos,
+                    gb["inv_temp"][:b], gb["top_k"][:b], gb["top_p_q"][:b],
+                    gb["seed"][:b], seq_lens, gb["script"][:b],
+                    gb["script_mask"][:b], gb["ctr"], gb["hist"][:, :b],
+                    tokens, gb["ticket"])
+                return
             if self._fused_sampler(logits):
                 lo, hi = self._valid_vocab
                 D.greedy_sample_step(
@@ -313,27 +441,54 @@ class Engine:
             gb["ctr"].add_(1)
             tokens.copy_(nxt)
 
-        rungs = ladder_rungs(B, DECODE_LADDER)
+        self._rungs = ladder_rungs(B, DECODE_LADDER)
+        self._gbuf = gb
+        self._graph_body = body
+        self._graph_pool = None
+        self._graphs = self._capture_ladder(sampled=False)
+        self._graph = self._graphs[B]
+
+    def _capture_ladder(self, sampled: bool) -> dict:
+        """One graph of the decode step per rung; both ladders draw on the
+        same memory pool."""
+        gb, body = self._gbuf, self._graph_body
         graphs: dict = {}
-        pool = None
-        for b in reversed(rungs):     # largest first: it sizes the pool
+        for b in reversed(self._rungs):   # largest first: it sizes the pool
             # warm up the exact captured ops (allocator + rocBLAS algo
             # selection)
             for _ in range(2):
-                body(b)
+                body(b, sampled)
             gb["ctr"].zero_()
             gb["seq_lens"].zero_()
             torch.cuda.synchronize()
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool):
-                body(b)
-            if pool is None:
-                pool = g.pool()
+            with torch.cuda.graph(g, pool=self._graph_pool):
+                body(b, sampled)
+            if self._graph_pool is None:
+                self._graph_pool = g.pool()
             graphs[b] = g
-        self._graphs = graphs
-        self._rungs = rungs
-        self._graph = graphs[B]
-        self._gbuf = gb
+        return graphs
+
+    def _ensure_sampled_graph(self) -> bool:
+        """Capture the second ladder, whose sampler is the per-request
+        kernel, the first time a run needs it.  The graph buffers are idle
+        here (no live row), so the warm-up steps write nothing into the KV
+        cache."""
+        if self._graphs_sampled:
+            return True
+        if self._sampled_failed:
+            return False
+        self._gbuf["active"].zero_()
+        self._gbuf["seq_lens"].zero_()
+        try:
+            self._graphs_sampled = self._capture_ladder(sampled=True)
+            return True
+        except Exception:
+            # as _ensure_graph: runs with sampled rows go eager from here on
+            self._sampled_failed = True
+            self._graphs_sampled = {}
+            torch.cuda.synchronize()
+            return False
 
     def _decode_run_eager(self, batch: list[Sequence], run: int) -> None:
         """Eager fallback for a graph run (capture unavailable)."""
@@ -357,7 +512,23 @@ class Engine:
         sl = self.kv.seq_lens_tensor(seq_ids)
         logits = self.model.forward_decode(tokens, self.kv, bt, sl,
                                            positions)
-        nxt = self._sample(logits).tolist()
+        own = [i for i, s in enumerate(batch) if s.sampling is not None]
+        if not own:
+            nxt = self._sample(logits).tolist()
+        else:
+            # rows that have `sampling` draw their own tokens, at the
+            # position of the token being drawn; the rest as ever
+            nxt = [0] * len(batch)
+            rest = [i for i, s in enumerate(batch) if s.sampling is None]
+            if rest:
+                for i, t in zip(rest, self._sample(logits[rest]).tolist()):
+                    nxt[i] = t
+            toks = self._sample_rows(
+                logits[own], [batch[i] for i in own],
+                [len(batch[i].prompt) + len(batch[i].out_tokens)
+                 for i in own])
+            for i, t in zip(own, toks):
+                nxt[i] = t
         for s, tok in zip(batch, nxt):
             if s.script:
                 # grammar-forced continuation (script index: out_tokens[0]
@@ -371,17 +542,32 @@ class Engine:
         self.stats.decode_steps += 1
         by_live = self.stats.decode_steps_by_live
         by_live[len(batch)] = by_live.get(len(batch), 0) + 1
+        which = "sampled" if any(s.sampled for s in batch) else "greedy"
+        self.stats.decode_steps_by_sampler[which] += 1
 
     def _decode_run_graph(self, batch: list[Sequence], run: int) -> None:
         """Run `run` decode steps for `batch` with zero host round trips:
-        pages are pre-extended, the graph self-feeds, one sync at the end."""
+        pages are pre-extended, the graph self-feeds, one sync at the end.
+        A run with a live row at a temperature of its own above 0 replays
+        the second ladder; every other run replays the first, whose greedy
+        token is also what a row with SamplingParams at temperature 0
+        draws.  (Under an engine-wide temperature above 0 the first
+        ladder's policy is not greedy, so runs with `sampling` rows go
+        eager there.)"""
         if not self._ensure_graph():
             self._decode_run_eager(batch, run)
             return
-        self._graph_run_begin(batch, run)
+        sampled = any(s.sampled for s in batch)
+        if (sampled and not self._ensure_sampled_graph()) or (
+                self.temperature > 0.0
+                and any(s.sampling is not None for s in batch)):
+            self._decode_run_eager(batch, run)
+            return
+        self._graph_run_begin(batch, run, sampled)
         self._graph_run_end(batch, run)
 
-    def _graph_run_begin(self, batch: list[Sequence], run: int) -> None:
+    def _graph_run_begin(self, batch: list[Sequence], run: int,
+                         sampled: bool = False) -> None:
         """Fill the graph buffers and queue `run` replays (async on the
         current stream — no host sync; _graph_run_end collects)."""
         gb = self._gbuf
@@ -429,13 +615,31 @@ class Engine:
         else:
             gb["script_mask"].fill_(False)
         gb["ctr"].zero_()
+        if sampled:
+            # rows without `sampling` (and the idle rows of the rung) are
+            # greedy rows of the per-request sampler
+            own = [s.sampling for s in batch]
+            gb["inv_temp"].zero_()
+            gb["inv_temp"][:n] = torch.tensor(
+                [p.inv_temp if p else 0.0 for p in own],
+                dtype=torch.float32, device=dev)
+            gb["top_k"][:n] = torch.tensor(
+                [p.top_k if p else 0 for p in own],
+                dtype=torch.int32, device=dev)
+            gb["top_p_q"][:n] = torch.tensor(
+                [p.top_p_q if p else 65536 for p in own],
+                dtype=torch.int32, device=dev)
+            gb["seed"][:n] = torch.tensor(
+                [_seed_i64(s.seed) if s.sampling else 0 for s in batch],
+                dtype=torch.int64, device=dev)
         if _TIMING:
             torch.cuda.synchronize()
             self._t_graph0 = time.perf_counter()
         # the rung depends on len(batch) alone, so the schedule and the
         # results stay a deterministic function of the inputs
         self._rung = pick_rung(self._rungs, n)
-        g = self._graphs[self._rung]
+        self._run_sampler = "sampled" if sampled else "greedy"
+        g = (self._graphs_sampled if sampled else self._graphs)[self._rung]
         for _ in range(run):
             g.replay()
 
@@ -460,15 +664,24 @@ class Engine:
         by_live[n] = by_live.get(n, 0) + run
         by_rung = self.stats.decode_steps_by_rung
         by_rung[self._rung] = by_rung.get(self._rung, 0) + run
+        self.stats.decode_steps_by_sampler[self._run_sampler] += run
 
     # ------------------------------------------------------------------
     def submit(self, prompt_tokens: list[int], max_new_tokens: int,
                continue_from: Sequence | None = None,
-               keep_alive: bool = False, constraint=None) -> Sequence:
+               keep_alive: bool = False, constraint=None,
+               sampling: SamplingParams | None = None) -> Sequence:
         """Queue a prompt.  continue_from: a completed keep-alive sequence
         whose prompt is a prefix of this one — its KV prefix is reused.
-        constraint: models.grammar.CompiledGrammar for this turn."""
+        constraint: models.grammar.CompiledGrammar for this turn.
+        sampling: this request's own SamplingParams (None: the engine-wide
+        policy); an open seed is drawn from the engine's seed generator and
+        the seed in use is kept on the sequence."""
         prompt = list(prompt_tokens[: self.max_seq_len - 1])
+        seed = None
+        if sampling is not None:
+            seed = sampling.seed if sampling.seed is not None \
+                else self._seed_rng.getrandbits(64)
         decision_allowed = branches = None
         if constraint is not None:
             decision_allowed = list(constraint.decision_allowed)
@@ -494,7 +707,8 @@ class Engine:
                 seq = Sequence(continue_from.seq_id, prompt, max_new_tokens,
                                cached_len=shared, keep_alive=keep_alive,
                                decision_allowed=decision_allowed,
-                               branches=branches)
+                               branches=branches, sampling=sampling,
+                               seed=seed)
                 self.kv.truncate(seq.seq_id, shared)
                 self._next_id = max(self._next_id, seq.seq_id + 1)
                 self.pending.append(seq)
@@ -502,7 +716,8 @@ class Engine:
             self.kv.free(continue_from.seq_id)
         seq = Sequence(self._next_id, prompt, max_new_tokens,
                        keep_alive=keep_alive,
-                       decision_allowed=decision_allowed, branches=branches)
+                       decision_allowed=decision_allowed, branches=branches,
+                       sampling=sampling, seed=seed)
         self._next_id += 1
         self.pending.append(seq)
         return seq
@@ -691,10 +906,25 @@ class Engine:
         self.stats.wall_s += time.perf_counter() - t0
 
     def generate_batch(self, prompts: list[list[int]],
-                       max_new_tokens: list[int]) -> list[list[int]]:
-        seqs = [self.submit(p, m) for p, m in zip(prompts, max_new_tokens)]
+                       max_new_tokens: list[int],
+                       sampling=None) -> list[list[int]]:
+        """sampling: one SamplingParams for every prompt, or a list with
+        one entry (or None) per prompt."""
+        per = _per_prompt(sampling, len(prompts))
+        seqs = [self.submit(p, m, sampling=sp)
+                for p, m, sp in zip(prompts, max_new_tokens, per)]
         self.run_to_completion()
         return [s.out_tokens for s in seqs]
+
+
+def _per_prompt(sampling, n: int) -> list:
+    """One SamplingParams (or None) per prompt from one value or a list."""
+    if isinstance(sampling, (list, tuple)):
+        if len(sampling) != n:
+            raise ValueError(f"{len(sampling)} sampling entries for {n} "
+                             "prompts")
+        return list(sampling)
+    return [sampling] * n
 
 
 class EngineLLM:
@@ -717,8 +947,12 @@ class EngineLLM:
 
     def __call__(self, prompts: list[str], max_new_tokens: list[int],
                  conv_ids: list | None = None,
-                 grammars: list | None = None) -> list[str]:
+                 grammars: list | None = None,
+                 sampling=None) -> list[str]:
+        """sampling: one SamplingParams for every prompt, or a list with
+        one entry (or None) per prompt."""
         from .grammar import compile_grammar
+        per = _per_prompt(sampling, len(prompts))
         seqs = []
         for i, (p, m) in enumerate(zip(prompts, max_new_tokens)):
             conv = conv_ids[i] if conv_ids is not None else None
@@ -729,7 +963,8 @@ class EngineLLM:
             enc = self.tokenizer.encode(p)
             seq = self.engine.submit(enc, m, continue_from=prev,
                                      keep_alive=conv is not None,
-                                     constraint=constraint)
+                                     constraint=constraint,
+                                     sampling=per[i])
             if conv is not None:
                 self._convs[conv] = seq
             seqs.append(seq)
@@ -738,7 +973,7 @@ class EngineLLM:
 
     # ---- event-driven (continuous) scheduling interface ----------------
     def submit_turn(self, conv_id, prompt: str, max_new_tokens: int,
-                    grammar=None) -> None:
+                    grammar=None, sampling=None) -> None:
         """Queue one agent turn WITHOUT running the engine — the
         continuous scheduler (agents/schedule.py) interleaves engine
         slices with tool I/O so turns join the running batch as they
@@ -748,7 +983,8 @@ class EngineLLM:
         prev = self._convs.get(conv_id)
         enc = self.tokenizer.encode(prompt)
         seq = self.engine.submit(enc, max_new_tokens, continue_from=prev,
-                                 keep_alive=True, constraint=constraint)
+                                 keep_alive=True, constraint=constraint,
+                                 sampling=sampling)
         self._convs[conv_id] = seq
         self._by_seq[id(seq)] = conv_id
 

@@ -462,6 +462,216 @@ def greedy_sample_step(logits: torch.Tensor, lo: int, hi: int, eos: int,
     ctr.add_(1)
 
 
+# ---- per-request seeded sampling -----------------------------------------
+#
+# The sampling rule (the CPU branch below is the specification; the kernel,
+# ops/hip/sampling.hip, agrees with it bit for bit).  Per row: bf16
+# logits[V]; the window lo, hi, eos of greedy_sample_step; inv_temp (f32);
+# top_k (i32, 0 = off); top_p_q (i32 in [1, 65536], 65536 = off); seed (64
+# bits); pos (i32).  A row's token depends on these alone.
+#
+# Candidates: the indices in [lo, hi) U {eos}, in ascending index order.
+# Greedy rows: inv_temp == 0 gives the greedy_sample_step token, the
+#   lowest-index argmax over the candidates (0 if all are -inf); the other
+#   parameters are ignored.
+# Weight: m = the maximum candidate logit; m == -inf gives token 0.  In f32,
+#   every operation rounded on its own (no FMA):
+#     d = l - m;  x = d * inv_temp;  y = max(x * LOG2E, -64)
+#     n = floor(y + 0.5);  f = y - n
+#     p = Horner(f), coefficients c_k = f32(ln2^k / k!), k = 6..0: the
+#         degree-6 Taylor polynomial of 2^f on [-0.5, 0.5], remainder at
+#         most (ln2/2)^7/7! ~ 1.2e-7
+#     q = (u32) trunc(p * 2^24)
+#     w = ((u64) q << 16) >> (-n) when -n <= 40, else 0
+#   The maximum has w = 2^40, totals stay below 2^58, and a token below
+#   2^-40 of the maximum has weight 0 and is never drawn.
+# Key: the order-preserving 16-bit key of the bf16 logit.  The weight
+#   depends on the logit alone, so thresholds are thresholds on the key.
+# top-k: tau_k = the largest key with count(key >= tau_k) >= top_k, the
+#   smallest key if there are fewer candidates than top_k.  Ties at the
+#   threshold are all kept.
+# top-p, on what top-k kept: total_k = sum of w;
+#   need = max(1, floor(total_k * top_p_q / 2^16)) (an exact integer);
+#   tau_p = the largest key with sum over key >= tau_p of w >= need.  Ties
+#   are kept.
+# Kept set: key >= max(tau_k, tau_p); total = the sum of w over it.
+# Draw: Philox4x32-10 (constants 0xD2511F53, 0xCD9E8D57, 0x9E3779B9,
+#   0xBB67AE85), key (seed & 0xffffffff, seed >> 32), counter (pos, 0, 0, 0);
+#   r = x0 | x1 << 32; target = (r * total) >> 64; the token is the first
+#   kept candidate, in ascending index, whose running sum of w exceeds
+#   target.
+# Everything after the weight is integer arithmetic, so no reduction order
+# can change a bit.
+
+_LOG2E = 1.4426950408889634
+_M32 = 0xffffffff
+
+
+def _exp2_coeffs() -> list[float]:
+    import math
+    return [float(torch.tensor(math.log(2.0) ** k / math.factorial(k),
+                               dtype=torch.float64).float())
+            for k in range(7)]
+
+
+def _mulhi32(a: int, b: torch.Tensor) -> torch.Tensor:
+    """High word of a * b, a and b below 2^32, in int64 without overflow."""
+    return (a * (b >> 16) + ((a * (b & 0xffff)) >> 16)) >> 16
+
+
+def philox4x32_10(counter: torch.Tensor, key: torch.Tensor) -> torch.Tensor:
+    """Philox4x32-10 on int64 tensors of 32-bit words: counter [N, 4],
+    key [N, 2] -> [N, 4]."""
+    c0, c1, c2, c3 = (counter[:, i].clone() for i in range(4))
+    k0, k1 = key[:, 0].clone(), key[:, 1].clone()
+    for _ in range(10):
+        hi0, lo0 = _mulhi32(0xD2511F53, c0), (0xD2511F53 * c0) & _M32
+        hi1, lo1 = _mulhi32(0xCD9E8D57, c2), (0xCD9E8D57 * c2) & _M32
+        c0, c1, c2, c3 = hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0
+        k0 = (k0 + 0x9E3779B9) & _M32
+        k1 = (k1 + 0xBB67AE85) & _M32
+    return torch.stack([c0, c1, c2, c3], dim=1)
+
+
+def sample_key(logits: torch.Tensor) -> torch.Tensor:
+    """Order-preserving 16-bit key (int64) of bf16 logits."""
+    bits = logits.contiguous().view(torch.int16).to(torch.int64) & 0xffff
+    return torch.where((bits & 0x8000) != 0, ~bits & 0xffff, bits | 0x8000)
+
+
+def sample_weights(logits: torch.Tensor, m: torch.Tensor,
+                   inv_temp: torch.Tensor) -> torch.Tensor:
+    """The rule's integer weights (int64) of bf16 logits [B, C] against the
+    row maxima m [B] (f32, finite) and inv_temp [B] (f32, > 0)."""
+    f32 = torch.float32
+    c = _exp2_coeffs()
+    d = logits.float() - m[:, None]
+    x = d * inv_temp[:, None]
+    y = torch.maximum(x * torch.tensor(_LOG2E, dtype=f32),
+                      torch.tensor(-64.0, dtype=f32))
+    n = torch.floor(y + 0.5)
+    f = y - n
+    p = torch.full_like(f, c[6])
+    for k in range(5, -1, -1):
+        p = p * f
+        p = p + torch.tensor(c[k], dtype=f32)
+    q = (p * 16777216.0).to(torch.int64)
+    sh = (-n).to(torch.int64)
+    return torch.where(sh <= 40, (q << 16) >> sh.clamp(max=40),
+                       torch.zeros_like(q))
+
+
+def _candidates(lo: int, hi: int, eos: int) -> list[int]:
+    idx = list(range(lo, hi))
+    if 0 <= eos < lo:
+        idx.insert(0, eos)
+    elif eos >= hi:
+        idx.append(eos)
+    return idx
+
+
+def _sample_rows_cpu(logits, lo, hi, eos, inv_temp, top_k, top_p_q, seed,
+                     pos) -> torch.Tensor:
+    B = logits.shape[0]
+    idx = _candidates(lo, hi, eos)
+    C = len(idx)
+    if B == 0 or C == 0:
+        return torch.zeros(B, dtype=torch.int64)
+    cand = torch.tensor(idx, dtype=torch.int64)
+    L = logits[:, cand]
+    lf = L.float()
+    m = lf.max(dim=1).values
+    dead = m == float("-inf")
+    # lowest candidate position among ties; an all -inf set gives token 0
+    greedy = cand[(lf == m[:, None]).int().argmax(dim=1)]
+    greedy = torch.where(dead, torch.zeros_like(greedy), greedy)
+    inv_temp = inv_temp[:B].float()
+    sampled = (inv_temp != 0) & ~dead
+    if not bool(sampled.any()):
+        return greedy
+    rows = sampled.nonzero(as_tuple=True)[0]
+    R = rows.numel()
+    L = L[rows]
+    key = sample_key(L)
+    w = sample_weights(L, m[rows], inv_temp[rows])
+    k = top_k[:B][rows].to(torch.int64)
+    pq = top_p_q[:B][rows].to(torch.int64)
+    skey, order = key.sort(dim=1, descending=True, stable=True)
+    cum = w.gather(1, order).cumsum(dim=1)
+    tau_k = skey.gather(1, (k.clamp(1, C) - 1)[:, None]).squeeze(1)
+    tau_k = torch.where(k > 0, tau_k, torch.zeros_like(tau_k))
+    nk = (skey >= tau_k[:, None]).sum(dim=1)
+    total_k = cum.gather(1, (nk - 1)[:, None]).squeeze(1)
+    need = torch.tensor([max(1, (t * q) >> 16)
+                         for t, q in zip(total_k.tolist(), pq.tolist())],
+                        dtype=torch.int64)
+    jp = (cum < need[:, None]).sum(dim=1)
+    tau_p = skey.gather(1, jp[:, None]).squeeze(1)
+    tau = torch.maximum(tau_k, tau_p)
+    run = torch.where(key >= tau[:, None], w, torch.zeros_like(w)) \
+        .cumsum(dim=1)
+    total = run[:, -1]
+    sd = seed[:B][rows].to(torch.int64)
+    zero = torch.zeros(R, dtype=torch.int64)
+    x = philox4x32_10(
+        torch.stack([pos[:B][rows].to(torch.int64) & _M32, zero, zero, zero],
+                    dim=1),
+        torch.stack([sd & _M32, (sd >> 32) & _M32], dim=1))
+    target = torch.tensor(
+        [((x0 | (x1 << 32)) * t) >> 64
+         for x0, x1, t in zip(x[:, 0].tolist(), x[:, 1].tolist(),
+                              total.tolist())], dtype=torch.int64)
+    tok = cand[(run <= target[:, None]).sum(dim=1)]
+    out = greedy.clone()
+    out[rows] = tok
+    return out
+
+
+def sample_tokens(logits: torch.Tensor, lo: int, hi: int, eos: int,
+                  inv_temp: torch.Tensor, top_k: torch.Tensor,
+                  top_p_q: torch.Tensor, seed: torch.Tensor,
+                  pos: torch.Tensor) -> torch.Tensor:
+    """The draw of the sampling rule above for each row of bf16 logits
+    [B, V], no bookkeeping -> tokens i64 [B].  inv_temp f32, top_k /
+    top_p_q / pos i32, seed i64 (the 64 bits, two's complement), each of
+    at least B rows."""
+    if logits.is_cuda:
+        return ext().sample_tokens(logits, lo, hi, eos, inv_temp, top_k,
+                                   top_p_q, seed, pos)
+    if logits.dtype != torch.bfloat16:
+        raise RuntimeError("sample_tokens: logits must be bf16")
+    return _sample_rows_cpu(logits, lo, hi, eos, inv_temp, top_k, top_p_q,
+                            seed, pos)
+
+
+def sample_step(logits: torch.Tensor, lo: int, hi: int, eos: int,
+                inv_temp: torch.Tensor, top_k: torch.Tensor,
+                top_p_q: torch.Tensor, seed: torch.Tensor, pos: torch.Tensor,
+                script: torch.Tensor, script_mask: torch.Tensor,
+                ctr: torch.Tensor, hist: torch.Tensor, tokens: torch.Tensor,
+                ticket: torch.Tensor | None = None) -> None:
+    """One decode step's per-request sampling and bookkeeping, in place:
+    greedy_sample_step with tok[b] drawn by the sampling rule above (rows
+    with inv_temp == 0 draw the greedy token)."""
+    if logits.is_cuda:
+        ext().sample_step(logits, lo, hi, eos, inv_temp, top_k, top_p_q,
+                          seed, pos, script, script_mask, ctr, hist, tokens,
+                          ticket)
+        return
+    B = logits.shape[0]
+    if B == 0:
+        return
+    tok = sample_tokens(logits, lo, hi, eos, inv_temp, top_k, top_p_q, seed,
+                        pos)
+    c = int(ctr[0])
+    j = min(max(c, 0), script.shape[1] - 1)
+    tok = torch.where(script_mask[:B, j], script[:B, j], tok)
+    if 0 <= c < hist.shape[0]:
+        hist[c, :B] = tok
+    tokens[:B] = tok
+    ctr.add_(1)
+
+
 # ---- retrieval / streaming ------------------------------------------------
 
 def topk_cosine(queries: torch.Tensor, docs: torch.Tensor, k: int):

@@ -83,5 +83,11 @@ __device__ __forceinline__ float block_reduce_sum(float v, float* scratch) {
   return total;
 }
 
-#define QSA_CHECK(cond, msg)                                            \
+// ---- running argmax, lowest index on ties (the samplers) ------------------
+__device__ __forceinline__ void qsa_argmax_take(float& bv, int& bi, float v,
+                                                int i) {
+  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
+}
+
+#define QSA_CHECK(cond, msg)                                           \
   TORCH_CHECK(cond, "qsa_hip: ", msg)

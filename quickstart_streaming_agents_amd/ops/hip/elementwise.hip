@@ -368,11 +368,6 @@ extern "C" void qsa_softmax_rows_bf16_launch(unsigned short* scores,
 // (ticket counter, reset for the next launch), so no workgroup can observe
 // the advanced value.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void qsa_argmax_take(float& bv, int& bi, float v,
-                                                int i) {
-  if (v > bv || (v == bv && i < bi)) { bv = v; bi = i; }
-}
-
 __global__ void __launch_bounds__(256)
 qsa_greedy_sample_kernel(const unsigned short* __restrict__ logits,  // [B,V]
                          long long V, int lo, int hi, int eos,

@@ -114,6 +114,11 @@ extern "C" void qsa_greedy_sample_launch(
     const unsigned short*, int, long long, int, int, int, const long long*,
     const unsigned char*, int, long long*, long long*, long long, int,
     long long*, unsigned int*, hipStream_t);
+extern "C" void qsa_sample_launch(
+    const unsigned short*, int, long long, int, int, int, const float*,
+    const int*, const int*, const long long*, const int*, const long long*,
+    const unsigned char*, int, long long*, long long*, long long, int,
+    long long*, unsigned int*, hipStream_t);
 extern "C" void qsa_gemm_fp8_batch_launch(const unsigned short*,
                                           const unsigned char*,
                                           const float*, unsigned short*,
@@ -882,6 +887,101 @@ void greedy_sample_step(torch::Tensor logits, long lo, long hi, long eos,
       reinterpret_cast<unsigned int*>(ticket.data_ptr<int>()), cur_stream());
 }
 
+// Checks shared by sample_step and sample_tokens (sampling.hip): the logits,
+// the window and the per-row parameter buffers, each of at least B rows.
+static void check_sample_rows(const torch::Tensor& logits, long lo, long hi,
+                              long eos, const torch::Tensor& inv_temp,
+                              const torch::Tensor& top_k,
+                              const torch::Tensor& top_p_q,
+                              const torch::Tensor& seed,
+                              const torch::Tensor& pos) {
+  CHK_DEV(logits); CHK_CONT(logits); CHK_BF16(logits);
+  TORCH_CHECK(logits.dim() == 2, "logits [B, V]");
+  const long long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(0 <= lo && lo <= hi && hi <= V, "0 <= lo <= hi <= V");
+  TORCH_CHECK(eos < V, "eos < V");
+  // the kernel keeps one LDS total per 2048 candidates, 2048 of them (two
+  // go to the window's unaligned ends); at 2^40 per candidate the weight
+  // totals stay far inside 64 bits
+  TORCH_CHECK(V <= 2046LL * 2048, "V <= 2046 * 2048");
+  CHK_DEV(inv_temp); CHK_CONT(inv_temp); CHK_F32(inv_temp);
+  CHK_DEV(top_k); CHK_CONT(top_k); CHK_I32(top_k);
+  CHK_DEV(top_p_q); CHK_CONT(top_p_q); CHK_I32(top_p_q);
+  CHK_DEV(seed); CHK_CONT(seed);
+  TORCH_CHECK(seed.scalar_type() == at::kLong, "seed must be i64");
+  CHK_DEV(pos); CHK_CONT(pos); CHK_I32(pos);
+  TORCH_CHECK(inv_temp.dim() == 1 && inv_temp.numel() >= B &&
+                  top_k.dim() == 1 && top_k.numel() >= B &&
+                  top_p_q.dim() == 1 && top_p_q.numel() >= B &&
+                  seed.dim() == 1 && seed.numel() >= B && pos.dim() == 1 &&
+                  pos.numel() >= B,
+              "inv_temp / top_k / top_p_q / seed / pos: 1-D, >= B rows");
+}
+
+void sample_step(torch::Tensor logits, long lo, long hi, long eos,
+                 torch::Tensor inv_temp, torch::Tensor top_k,
+                 torch::Tensor top_p_q, torch::Tensor seed, torch::Tensor pos,
+                 torch::Tensor script, torch::Tensor script_mask,
+                 torch::Tensor ctr, torch::Tensor hist, torch::Tensor tokens,
+                 torch::Tensor ticket) {
+  // One decode step's per-request sampling + bookkeeping in one launch
+  // (sampling.hip): tokens/hist/ctr are updated in place.
+  check_sample_rows(logits, lo, hi, eos, inv_temp, top_k, top_p_q, seed, pos);
+  CHK_DEV(script); CHK_CONT(script); CHK_DEV(script_mask);
+  CHK_CONT(script_mask); CHK_DEV(ctr); CHK_DEV(hist); CHK_DEV(tokens);
+  CHK_CONT(tokens); CHK_DEV(ticket);
+  const long long B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK(script.scalar_type() == at::kLong && script.dim() == 2 &&
+                  script.size(0) >= B, "script i64 [>=B, max_run]");
+  TORCH_CHECK(script_mask.scalar_type() == at::kBool &&
+                  script_mask.sizes() == script.sizes(),
+              "script_mask bool, same shape as script");
+  TORCH_CHECK(script.size(1) >= 1, "max_run >= 1");
+  TORCH_CHECK(ctr.scalar_type() == at::kLong && ctr.numel() == 1, "ctr i64 [1]");
+  TORCH_CHECK(hist.scalar_type() == at::kLong && hist.dim() == 2 &&
+                  hist.size(1) >= B && hist.stride(1) == 1,
+              "hist i64 [rows, >=B], unit column stride");
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && tokens.numel() >= B,
+              "tokens i64 [>=B]");
+  TORCH_CHECK(ticket.scalar_type() == at::kInt && ticket.numel() == 1,
+              "ticket i32 [1]");
+  if (B == 0) return;
+  qsa_sample_launch(
+      u16(logits), (int)B, V, (int)lo, (int)hi, eos < 0 ? -1 : (int)eos,
+      inv_temp.data_ptr<float>(), top_k.data_ptr<int>(),
+      top_p_q.data_ptr<int>(),
+      reinterpret_cast<const long long*>(seed.data_ptr<int64_t>()),
+      pos.data_ptr<int>(),
+      reinterpret_cast<const long long*>(script.data_ptr<int64_t>()),
+      reinterpret_cast<const unsigned char*>(script_mask.data_ptr<bool>()),
+      (int)script.size(1),
+      reinterpret_cast<long long*>(ctr.data_ptr<int64_t>()),
+      reinterpret_cast<long long*>(hist.data_ptr<int64_t>()), hist.stride(0),
+      (int)hist.size(0),
+      reinterpret_cast<long long*>(tokens.data_ptr<int64_t>()),
+      reinterpret_cast<unsigned int*>(ticket.data_ptr<int>()), cur_stream());
+}
+
+torch::Tensor sample_tokens(torch::Tensor logits, long lo, long hi, long eos,
+                            torch::Tensor inv_temp, torch::Tensor top_k,
+                            torch::Tensor top_p_q, torch::Tensor seed,
+                            torch::Tensor pos) {
+  // The draw of sample_step alone: no script, history or counter.
+  check_sample_rows(logits, lo, hi, eos, inv_temp, top_k, top_p_q, seed, pos);
+  const long long B = logits.size(0), V = logits.size(1);
+  auto tokens = torch::empty({B}, logits.options().dtype(torch::kInt64));
+  if (B == 0) return tokens;
+  qsa_sample_launch(
+      u16(logits), (int)B, V, (int)lo, (int)hi, eos < 0 ? -1 : (int)eos,
+      inv_temp.data_ptr<float>(), top_k.data_ptr<int>(),
+      top_p_q.data_ptr<int>(),
+      reinterpret_cast<const long long*>(seed.data_ptr<int64_t>()),
+      pos.data_ptr<int>(), nullptr, nullptr, 1, nullptr, nullptr, 0, 0,
+      reinterpret_cast<long long*>(tokens.data_ptr<int64_t>()), nullptr,
+      cur_stream());
+  return tokens;
+}
+
 std::vector<torch::Tensor> topk_cosine(torch::Tensor queries,
                                        torch::Tensor docs, long k) {
   CHK_DEV(queries); CHK_CONT(queries); CHK_F32(queries); CHK_F32(docs);
@@ -1006,6 +1106,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("greedy_sample_step", &greedy_sample_step,
         "fused greedy sampling step: windowed argmax, script override, "
         "history/token/counter update (in place)");
+  m.def("sample_step", &sample_step,
+        "fused per-request sampling step: seeded temperature / top-k / "
+        "top-p draw, script override, history/token/counter update "
+        "(in place)");
+  m.def("sample_tokens", &sample_tokens,
+        "the draw of sample_step alone -> tokens i64 [B]");
   m.def("topk_cosine", &topk_cosine, "exact cosine top-k over the HBM index");
   m.def("hash_build", &hash_build,
         "build latest-per-key hash table from (keys, event ts)");

@@ -31,6 +31,24 @@ from pydantic import BaseModel, Field
 class CompletionRequest(BaseModel):
     prompt: Union[str, list[str]]
     max_tokens: int = Field(default=64, ge=1, le=4096)
+    # per-request sampling (models/serve.py SamplingParams); the defaults
+    # are the engine-wide policy
+    temperature: float = Field(default=0.0, ge=0.0, le=2.0)
+    top_p: float = Field(default=1.0, gt=0.0, le=1.0)
+    top_k: int = Field(default=0, ge=0)
+    seed: Optional[int] = Field(default=None, ge=0, le=2 ** 63 - 1)
+
+    def sampling(self, n: int):
+        """One SamplingParams per prompt (prompt i draws under seed + i),
+        or None when every field is at its default."""
+        if self.temperature == 0.0 and self.top_p == 1.0 and \
+                self.top_k == 0 and self.seed is None:
+            return None
+        from .models.serve import SamplingParams
+        return [SamplingParams(
+            temperature=self.temperature, top_k=self.top_k, top_p=self.top_p,
+            seed=None if self.seed is None else self.seed + i)
+            for i in range(n)]
 
 
 class EmbeddingRequest(BaseModel):
@@ -69,6 +87,11 @@ def create_app(llm: Callable[[list[str], list[int]], list[str]],
     app.state.started = time.time()
     app.state.requests = 0
     agents = agents or {}
+    # two-argument callables (the CPU stub) serve default requests only
+    import inspect
+    llm_params = inspect.signature(llm).parameters.values()
+    takes_sampling = any(p.name == "sampling" or p.kind is p.VAR_KEYWORD
+                         for p in llm_params)
 
     @app.get("/healthz")
     def healthz():
@@ -173,7 +196,15 @@ def create_app(llm: Callable[[list[str], list[int]], list[str]],
         prompts = [req.prompt] if isinstance(req.prompt, str) else req.prompt
         if not prompts:
             raise HTTPException(400, "empty prompt list")
-        texts = llm(prompts, [req.max_tokens] * len(prompts))
+        sampling = req.sampling(len(prompts))
+        if sampling is None:
+            texts = llm(prompts, [req.max_tokens] * len(prompts))
+        elif not takes_sampling:
+            raise HTTPException(
+                501, "this deployment's LLM takes no sampling parameters")
+        else:
+            texts = llm(prompts, [req.max_tokens] * len(prompts),
+                        sampling=sampling)
         _observe("completions", t0)
         return {"object": "text_completion",
                 "choices": [{"index": i, "text": t}

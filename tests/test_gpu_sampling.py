@@ -1,0 +1,202 @@
+"""Per-request seeded sampling on the GPU: the kernel (ops/hip/sampling.hip)
+against the CPU branch of ops/dispatch.py, bit for bit; its host checks; the
+engine's second ladder of decode graphs against the eager engine; and the
+kernel's register allocation."""
+
+import os
+import sys
+
+import pytest
+import torch
+
+from test_decode_ladder import MAX_RUN, SAMPLER_CASES, sampler_case
+from test_gpu_decode_ladder import _prompts
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+
+# rows cycle through these, each list at its own period
+TEMPS = [0.0, 0.01, 0.7, 1.0, 1.5, 100.0]          # 0: a greedy row
+TOP_KS = [0, 1, 5, 50, 10 ** 6]
+TOP_PS = [65536, 58982, 32768, 1]
+POSITIONS = [0, 1, 5, 77, 4095, 2 ** 20, 2 ** 31 - 1]
+
+
+def row_params(B, offset):
+    """inv_temp, top_k, top_p_q, seed, pos for B rows (CPU tensors)."""
+    rows = [r + offset for r in range(B)]
+    inv = [0.0 if TEMPS[r % 6] == 0 else 1.0 / TEMPS[r % 6] for r in rows]
+    seeds = [(r * 0x9E3779B97F4A7C15 + 0xDEADBEEF00000001) % 2 ** 64
+             for r in rows]                          # high words set
+    seeds = [s - 2 ** 64 if s >= 2 ** 63 else s for s in seeds]
+    return (torch.tensor(inv, dtype=torch.float64).float(),
+            torch.tensor([TOP_KS[r % 5] for r in rows], dtype=torch.int32),
+            torch.tensor([TOP_PS[r % 4] for r in rows], dtype=torch.int32),
+            torch.tensor(seeds, dtype=torch.int64),
+            torch.tensor([POSITIONS[r % 7] for r in rows],
+                         dtype=torch.int32))
+
+
+def _run_case(B, V, lo, hi, eos, steps, ties=False):
+    from quickstart_streaming_agents_amd.ops import dispatch as D
+    e = -1 if eos is None else eos
+    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    for step in steps:
+        c = sampler_case(B, V, lo, hi, eos, seed=B * 1000 + step, step=step)
+        if not ties:
+            g = torch.Generator().manual_seed(V + 31 * step)
+            c["logits"] = (torch.randn(B, V, generator=g) * 3) \
+                .to(torch.bfloat16)
+        p = row_params(B, offset=step * 7 + B)
+        want = [c[k].clone() for k in ("tokens", "hist", "ctr")]
+        D.sample_step(c["logits"], lo, hi, e, *p, c["script"][:B],
+                      c["mask"][:B], want[2], want[1][:, :B], want[0])
+        got = [c[k].to(DEV) for k in ("tokens", "hist", "ctr")]
+        D.sample_step(c["logits"].to(DEV), lo, hi, e,
+                      *(t.to(DEV) for t in p), c["script"][:B].to(DEV),
+                      c["mask"][:B].to(DEV), got[2], got[1][:, :B], got[0],
+                      ticket)
+        torch.cuda.synchronize()
+        for name, a, b in zip(("tokens", "hist", "ctr"), got, want):
+            assert torch.equal(a.cpu(), b), (name, step)
+        assert int(ticket.item()) == 0      # reset for the next launch
+        # the draw alone gives the unscripted tokens
+        free = D.sample_tokens(c["logits"].to(DEV), lo, hi, e,
+                               *(t.to(DEV) for t in p)).cpu()
+        scripted = c["mask"][:B, step]
+        assert torch.equal(free[~scripted], want[0][:B][~scripted])
+
+
+@pytest.mark.parametrize("B,V,lo,hi,eos", SAMPLER_CASES + [
+    (3, 128256, 0, 128256, None),
+    (7, 2040, 3, 2037, None),
+    (4, 2048, 101, 106, 1),
+])
+def test_kernel_matches_cpu_branch(B, V, lo, hi, eos):
+    _run_case(B, V, lo, hi, eos, steps=(0, 3, MAX_RUN - 1))
+
+
+def test_kernel_matches_cpu_branch_full_batch():
+    _run_case(192, 128256, 16, 3335, 2, steps=(1,))
+
+
+def test_kernel_matches_cpu_branch_on_tie_logits():
+    _run_case(5, 2048, 16, 1000, 2, steps=(0, 3, MAX_RUN - 1), ties=True)
+    _run_case(3, 128256, 16, 3335, 128000, steps=(0,), ties=True)
+
+
+def test_host_checks_raise():
+    from quickstart_streaming_agents_amd.ops import dispatch as D
+    B, V = 4, 256
+    logits = torch.zeros(B, V, dtype=torch.bfloat16, device=DEV)
+    p = [t.to(DEV) for t in row_params(B, 0)]
+    assert D.sample_tokens(logits, 0, V, -1, *p).shape == (B,)
+    for lo, hi, eos in ((-1, 8, -1), (9, 8, -1), (0, V + 1, -1), (0, V, V)):
+        with pytest.raises(RuntimeError):
+            D.sample_tokens(logits, lo, hi, eos, *p)
+    for i in range(5):                      # each per-row buffer too short
+        short = list(p)
+        short[i] = short[i][:B - 1]
+        with pytest.raises(RuntimeError):
+            D.sample_tokens(logits, 0, V, -1, *short)
+    with pytest.raises(RuntimeError):
+        D.sample_tokens(logits.float(), 0, V, -1, *p)
+    with pytest.raises(RuntimeError):       # wrong parameter dtype
+        D.sample_tokens(logits, 0, V, -1, p[0].double(), *p[1:])
+    c = {k: (v.to(DEV) if torch.is_tensor(v) else v)
+         for k, v in sampler_case(B, V, 0, V, None, seed=1, step=0).items()}
+    ticket = torch.zeros(1, dtype=torch.int32, device=DEV)
+    with pytest.raises(RuntimeError):       # hist narrower than the batch
+        D.sample_step(logits, 0, V, -1, *p, c["script"][:B], c["mask"][:B],
+                      c["ctr"], c["hist"][:, :B - 1], c["tokens"], ticket)
+    torch.cuda.synchronize()
+
+
+# ---- engine ----------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def tiny_model():
+    from quickstart_streaming_agents_amd.models.llama import (LlamaConfig,
+                                                              LlamaModel)
+    return LlamaModel(LlamaConfig.preset("tiny"), device=DEV)
+
+
+def _engine(model, graph):
+    from quickstart_streaming_agents_amd.models.serve import Engine
+    eng = Engine(model, max_batch=48, max_seq_len=128, eos_id=2,
+                 valid_vocab=(16, 1000))
+    if not graph:
+        eng.use_graph = False
+    return eng
+
+
+def _mixed_sampling(n):
+    """Every other row sampled at T = 1.5 with mixed top-k / top-p."""
+    from quickstart_streaming_agents_amd.models.serve import SamplingParams
+    ks, ps = [0, 40, 0, 5], [1.0, 1.0, 0.9, 0.95]
+    return [SamplingParams(temperature=1.5, top_k=ks[(i // 2) % 4],
+                           top_p=ps[(i // 2) % 4], seed=100 + i)
+            if i % 2 == 0 else None for i in range(n)]
+
+
+def test_engine_sampled_ladder_matches_eager(tiny_model, monkeypatch):
+    from quickstart_streaming_agents_amd.models import serve
+    monkeypatch.setattr(serve, "DECODE_LADDER", True)
+    prompts, new = _prompts(20)
+    sampling = _mixed_sampling(20)
+    greedy = _engine(tiny_model, graph=False).generate_batch(prompts, new)
+    eager = _engine(tiny_model, graph=False).generate_batch(
+        prompts, new, sampling=sampling)
+    eng = _engine(tiny_model, graph=True)
+    out = eng.generate_batch(prompts, new, sampling=sampling)
+    assert eng._graph is not None, "graph capture failed"
+    assert eng._graphs_sampled and not eng._sampled_failed, \
+        "capture of the sampled ladder failed"
+    assert set(eng._graphs_sampled) == set(eng._rungs)
+    assert out == eager
+    by = eng.stats.decode_steps_by_sampler
+    assert by["sampled"] > 0
+    assert by["greedy"] + by["sampled"] == eng.stats.decode_steps
+    for i in range(1, 20, 2):               # the greedy rows
+        assert out[i] == greedy[i], i
+    assert any(out[i] != greedy[i] for i in range(0, 20, 2))
+
+
+def test_engine_all_greedy_never_captures_the_second_ladder(tiny_model,
+                                                            monkeypatch):
+    from quickstart_streaming_agents_amd.models import serve
+    monkeypatch.setattr(serve, "DECODE_LADDER", True)
+    prompts, new = _prompts(20)
+    eng = _engine(tiny_model, graph=True)
+    # SamplingParams at temperature 0 are greedy rows of the first ladder
+    sampling = [serve.SamplingParams() if i % 3 == 0 else None
+                for i in range(20)]
+    out = eng.generate_batch(prompts, new, sampling=sampling)
+    assert eng._graph is not None, "graph capture failed"
+    assert out == _engine(tiny_model, graph=False).generate_batch(prompts,
+                                                                  new)
+    assert eng.stats.decode_steps_by_sampler == {
+        "greedy": eng.stats.decode_steps, "sampled": 0}
+    assert eng._graphs_sampled == {}
+
+
+# ---- ISA -------------------------------------------------------------------
+
+def test_kernel_has_no_spills_or_scratch():
+    sys.path.insert(0, os.path.join(
+        os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    import tempfile
+
+    import isa_check
+    so = isa_check.find_so()
+    if so is None or not os.path.exists(isa_check.BUNDLER):
+        pytest.skip("built extension or ROCm LLVM tools unavailable")
+    with tempfile.TemporaryDirectory() as wd:
+        stats = isa_check.kernel_stats(isa_check.extract_hsacos(so, wd))
+    hits = {k: v for k, v in stats.items() if "qsa_sample_kernel" in k}
+    assert hits, "qsa_sample_kernel not in the built extension"
+    for name, st in hits.items():
+        assert st.get("vgpr_spill_count", 0) == 0, name
+        assert st.get("sgpr_spill_count", 0) == 0, name
+        assert st.get("private_segment_fixed_size", 0) == 0, name
