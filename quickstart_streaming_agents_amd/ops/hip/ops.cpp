@@ -200,6 +200,101 @@ static inline void chk_hd_strided(const torch::Tensor& t, int D,
               name, " must be a [B, H, D] view with contiguous heads");
 }
 
+// ---- argument checks shared by the attention and KV-writer bindings --------
+// Everything a kernel dereferences is checked here, ahead of the launch: the
+// kernels themselves trust their pointers.
+
+struct named_tensor {
+  const char* name;
+  const torch::Tensor& t;
+};
+
+// Every tensor argument lives on the first one's GPU: a CPU index array
+// would hand a host pointer to the kernel.
+static void chk_same_gpu(std::initializer_list<named_tensor> ts) {
+  const named_tensor& first = *ts.begin();
+  for (const named_tensor& a : ts) {
+    TORCH_CHECK(a.t.is_cuda(), a.name, " must be on the GPU");
+    TORCH_CHECK(a.t.device() == first.t.device(), a.name, " must be on ",
+                first.name, "'s device");
+  }
+}
+
+// bf16 [rows, heads, D] view with contiguous heads, D 64 or 128.
+static int chk_heads(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.scalar_type() == at::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 3, name, " must be [rows, heads, D]");
+  const int D = t.size(2);
+  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
+  chk_hd_strided(t, D, name);
+  return D;
+}
+
+// 16-byte fragment loads of a [rows, heads, D] view's rows.
+static void chk_rows16(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.stride(0) % 8 == 0 &&
+              reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0,
+              name, " rows must be 16-byte aligned");
+}
+
+// The paged cache pair for KVH kv heads of width D.
+static void chk_kv_cache(const torch::Tensor& kc, const torch::Tensor& vc,
+                         int KVH, int D) {
+  CHK_BF16(kc); CHK_BF16(vc); CHK_CONT(kc); CHK_CONT(vc);
+  TORCH_CHECK(kc.dim() == 5 && kc.size(1) == KVH && kc.size(2) == D / 8 &&
+              kc.size(3) == 64 && kc.size(4) == 8,
+              "K cache layout [P, KVH, D/8, 64, 8]");
+  TORCH_CHECK(vc.dim() == 4 && vc.size(2) == D && vc.size(3) == 64,
+              "V cache layout [P, KVH, D, 64] (transposed)");
+  TORCH_CHECK(vc.size(1) == KVH && vc.size(0) == kc.size(0),
+              "K and V caches must have the same pages and kv heads");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(kc.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(vc.data_ptr()) % 16 == 0,
+              "K/V caches must be 16-byte aligned");
+}
+
+// i32 contiguous index array of exactly n entries.
+static void chk_index(const torch::Tensor& t, long n, const char* name) {
+  TORCH_CHECK(t.scalar_type() == at::kInt, name, " must be i32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.numel() == n, name, " must have ", n, " entries");
+}
+
+// i32 contiguous [rows, >= 1 pages] block table.
+static void chk_block_table(const torch::Tensor& bt, long rows) {
+  CHK_I32(bt); CHK_CONT(bt);
+  TORCH_CHECK(bt.dim() == 2 && bt.size(0) == rows && bt.size(1) >= 1,
+              "block_table must be [", rows, ", pages >= 1]");
+}
+
+// f32 contiguous [positions, D/2] rope tables, 16-byte aligned.
+static void chk_rope_tables(const torch::Tensor& cos_t,
+                            const torch::Tensor& sin_t, int D) {
+  CHK_F32(cos_t); CHK_F32(sin_t); CHK_CONT(cos_t); CHK_CONT(sin_t);
+  TORCH_CHECK(cos_t.dim() == 2 && sin_t.dim() == 2 &&
+              cos_t.size(1) == D / 2 && sin_t.size(1) == D / 2 &&
+              cos_t.size(0) == sin_t.size(0),
+              "rope tables must be [positions, D/2]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(cos_t.data_ptr()) % 16 == 0 &&
+              reinterpret_cast<uintptr_t>(sin_t.data_ptr()) % 16 == 0,
+              "rope tables must be 16-byte aligned");
+}
+
+// New k/v rows of one step: both [rows, KVH, D] views with one row stride.
+static void chk_kv_rows(const torch::Tensor& k, const torch::Tensor& v,
+                        long rows, int KVH, int D) {
+  TORCH_CHECK(chk_heads(k, "k") == D && chk_heads(v, "v") == D &&
+              k.size(0) == rows && v.size(0) == rows && k.size(1) == KVH &&
+              v.size(1) == KVH, "k/v must be [", rows, ", KVH, D]");
+  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v strides must match");
+}
+
+// GQA: QH q heads over KVH kv heads, at most 16 per kv head.
+static void chk_gqa(int QH, int KVH) {
+  TORCH_CHECK(KVH > 0 && QH % KVH == 0, "GQA requires QH % KVH == 0");
+  TORCH_CHECK(QH / KVH <= 16, "GQA ratio <= 16");
+}
+
 void rope_inplace(torch::Tensor q, torch::Tensor k, torch::Tensor cos_t,
                   torch::Tensor sin_t, torch::Tensor pos) {
   CHK_DEV(q); CHK_BF16(q); CHK_BF16(k);
@@ -238,30 +333,36 @@ void softmax_rows_bf16_(torch::Tensor scores, double scale,
                                row_limits.data_ptr<int>(), cur_stream());
 }
 
-torch::Tensor paged_attn_decode(torch::Tensor q, torch::Tensor kc,
-                                torch::Tensor vc, torch::Tensor block_table,
-                                torch::Tensor seq_lens, double scale) {
-  CHK_DEV(q); CHK_BF16(q); CHK_BF16(kc); CHK_BF16(vc);
-  CHK_CONT(kc); CHK_CONT(vc); CHK_I32(block_table); CHK_I32(seq_lens);
-  CHK_CONT(block_table);
-  const int B = q.size(0), QH = q.size(1), D = q.size(2);
-  chk_hd_strided(q, D, "q");
-  const int KVH = kc.size(1);
-  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
-  TORCH_CHECK(QH % KVH == 0, "GQA requires QH % KVH == 0");
-  TORCH_CHECK(QH / KVH <= 16, "GQA ratio <= 16");
-  TORCH_CHECK(kc.size(2) == D / 8 && kc.size(3) == 64 && kc.size(4) == 8,
-              "K cache layout [P, KVH, D/8, 64, 8]");
-  TORCH_CHECK(vc.size(2) == D && vc.size(3) == 64,
-              "V cache layout [P, KVH, D, 64] (transposed)");
-  const int max_pages = block_table.size(1);
-  auto out = torch::empty({B, QH, D}, q.options());
-  // flash-decoding split count: fill the 256-CU chip (one WAVE per
-  // (b, kvh, split); 4 splits share a workgroup)
+// Flash-decoding split count of both decode bindings: it fixes the split
+// boundaries and with them the rounding, so the two must never drift apart
+// (tests/test_gpu_decode_fused.py compares bits).  Needs B * KVH > 0.
+static int decode_num_splits(int B, int KVH, int max_pages) {
   int ns = (int)std::min<long long>(32, std::max<long long>(
       1, (2048 + (long long)B * KVH - 1) / ((long long)B * KVH)));
   if (ns > 1) ns = std::max(ns, 4);   // fill all 4 waves per workgroup
-  ns = std::min(ns, std::max(1, max_pages));
+  return std::min(ns, std::max(1, max_pages));
+}
+
+torch::Tensor paged_attn_decode(torch::Tensor q, torch::Tensor kc,
+                                torch::Tensor vc, torch::Tensor block_table,
+                                torch::Tensor seq_lens, double scale) {
+  chk_same_gpu({{"q", q}, {"kc", kc}, {"vc", vc},
+                {"block_table", block_table}, {"seq_lens", seq_lens}});
+  const int D = chk_heads(q, "q");
+  const int B = q.size(0), QH = q.size(1);
+  chk_rows16(q, "q");
+  TORCH_CHECK(kc.dim() == 5, "K cache layout [P, KVH, D/8, 64, 8]");
+  const int KVH = kc.size(1);
+  chk_gqa(QH, KVH);
+  chk_kv_cache(kc, vc, KVH, D);
+  chk_block_table(block_table, B);
+  chk_index(seq_lens, B, "seq_lens");
+  const int max_pages = block_table.size(1);
+  auto out = torch::empty({B, QH, D}, q.options());
+  if (B == 0) return out;
+  // flash-decoding split count: fill the 256-CU chip (one WAVE per
+  // (b, kvh, split); 4 splits share a workgroup)
+  const int ns = decode_num_splits(B, KVH, max_pages);
   auto opts_f = q.options().dtype(at::kFloat);
   auto part_o = torch::empty({B, QH, ns, D}, opts_f);
   auto part_ml = torch::empty({B, QH, ns, 2}, opts_f);
@@ -271,16 +372,6 @@ torch::Tensor paged_attn_decode(torch::Tensor q, torch::Tensor kc,
       part_ml.data_ptr<float>(), u16m(out), (float)scale, B, QH, KVH,
       max_pages, D, q.stride(0), ns, cur_stream());
   return out;
-}
-
-// Flash-decoding split count, derived exactly as paged_attn_decode derives
-// it: it fixes the split boundaries and with them the rounding, so the two
-// must never drift apart (tests/test_gpu_decode_fused.py compares bits).
-static int decode_num_splits(int B, int KVH, int max_pages) {
-  int ns = (int)std::min<long long>(32, std::max<long long>(
-      1, (2048 + (long long)B * KVH - 1) / ((long long)B * KVH)));
-  if (ns > 1) ns = std::max(ns, 4);   // fill all 4 waves per workgroup
-  return std::min(ns, std::max(1, max_pages));
 }
 
 // One launch for a decode step's attention: RoPE on q (in registers) and on
@@ -296,38 +387,27 @@ torch::Tensor decode_attn_fused(torch::Tensor q, torch::Tensor k,
                                 torch::Tensor block_table,
                                 torch::Tensor seq_lens, double scale,
                                 int64_t waves_per_simd) {
-  CHK_DEV(q); CHK_BF16(q); CHK_BF16(k); CHK_BF16(v); CHK_BF16(kc);
-  CHK_BF16(vc); CHK_CONT(kc); CHK_CONT(vc); CHK_F32(cos_t); CHK_F32(sin_t);
-  CHK_CONT(cos_t); CHK_CONT(sin_t); CHK_I32(block_table); CHK_I32(seq_lens);
-  CHK_CONT(block_table);
-  const int B = q.size(0), QH = q.size(1), D = q.size(2);
+  chk_same_gpu({{"q", q}, {"k", k}, {"v", v}, {"kc", kc}, {"vc", vc},
+                {"cos_t", cos_t}, {"sin_t", sin_t},
+                {"block_table", block_table}, {"seq_lens", seq_lens}});
+  const int D = chk_heads(q, "q");
+  const int B = q.size(0), QH = q.size(1);
+  TORCH_CHECK(kc.dim() == 5, "K cache layout [P, KVH, D/8, 64, 8]");
   const int KVH = kc.size(1);
-  chk_hd_strided(q, D, "q"); chk_hd_strided(k, D, "k");
-  chk_hd_strided(v, D, "v");
-  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v strides must match");
-  TORCH_CHECK(k.size(0) == B && v.size(0) == B && k.size(1) == KVH &&
-              v.size(1) == KVH && k.size(2) == D && v.size(2) == D,
-              "k/v must be [B, KVH, D]");
-  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
-  TORCH_CHECK(QH % KVH == 0, "GQA requires QH % KVH == 0");
-  TORCH_CHECK(QH / KVH <= 16, "GQA ratio <= 16");
-  TORCH_CHECK(kc.size(2) == D / 8 && kc.size(3) == 64 && kc.size(4) == 8,
-              "K cache layout [P, KVH, D/8, 64, 8]");
-  TORCH_CHECK(vc.size(2) == D && vc.size(3) == 64,
-              "V cache layout [P, KVH, D, 64] (transposed)");
-  TORCH_CHECK(cos_t.size(1) == D / 2 && sin_t.size(1) == D / 2,
-              "rope tables must be [positions, D/2]");
-  // 16-byte fragment loads of q/k/v rows
-  TORCH_CHECK(q.stride(0) % 8 == 0 && k.stride(0) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0 &&
-              reinterpret_cast<uintptr_t>(k.data_ptr()) % 16 == 0,
-              "q/k rows must be 16-byte aligned");
+  chk_gqa(QH, KVH);
+  chk_kv_rows(k, v, B, KVH, D);
+  chk_kv_cache(kc, vc, KVH, D);
+  chk_rope_tables(cos_t, sin_t, D);
+  // 16-byte fragment loads of q rows and of the new k row (v is read by
+  // element)
+  chk_rows16(q, "q"); chk_rows16(k, "k");
   TORCH_CHECK(waves_per_simd == 1 || waves_per_simd == 2,
               "waves_per_simd must be 1 or 2");
-  TORCH_CHECK(seq_lens.numel() == B && block_table.size(0) == B,
-              "one seq_len / block-table row per sequence");
+  chk_block_table(block_table, B);
+  chk_index(seq_lens, B, "seq_lens");
   const int max_pages = block_table.size(1);
   auto out = torch::empty({B, QH, D}, q.options());
+  if (B == 0) return out;
   const int ns = decode_num_splits(B, KVH, max_pages);
   // NS <= 4 merges inside the workgroup: no partial buffers at all
   torch::Tensor part_o, part_ml;
@@ -352,15 +432,49 @@ torch::Tensor decode_attn_fused(torch::Tensor q, torch::Tensor k,
 void kv_append(torch::Tensor knew, torch::Tensor vnew, torch::Tensor kc,
                torch::Tensor vc, torch::Tensor block_table,
                torch::Tensor seq_lens) {
-  CHK_DEV(knew); CHK_BF16(knew); CHK_BF16(vnew);
-  CHK_I32(block_table); CHK_I32(seq_lens);
-  const int B = knew.size(0), KVH = knew.size(1), D = knew.size(2);
-  chk_hd_strided(knew, D, "knew"); chk_hd_strided(vnew, D, "vnew");
-  TORCH_CHECK(knew.stride(0) == vnew.stride(0), "k/v row strides must match");
+  chk_same_gpu({{"knew", knew}, {"vnew", vnew}, {"kc", kc}, {"vc", vc},
+                {"block_table", block_table}, {"seq_lens", seq_lens}});
+  const int D = chk_heads(knew, "knew");
+  const int B = knew.size(0), KVH = knew.size(1);
+  chk_kv_rows(knew, vnew, B, KVH, D);
+  chk_kv_cache(kc, vc, KVH, D);
+  chk_block_table(block_table, B);
+  chk_index(seq_lens, B, "seq_lens");
+  if (B == 0 || KVH == 0) return;
   qsa_kv_append_launch(u16(knew), u16(vnew), u16m(kc), u16m(vc),
                        block_table.data_ptr<int>(), seq_lens.data_ptr<int>(),
                        B, KVH, D, (int)block_table.size(1), knew.stride(0),
                        cur_stream());
+}
+
+// Checks common to the two prefill bindings; `map_item` / `map_pos0` are the
+// per-block (16 rows) or per-tile (32/64 rows) maps.  Returns D.
+static int chk_prefill_args(const torch::Tensor& q, const torch::Tensor& kc,
+                            const torch::Tensor& vc,
+                            const torch::Tensor& block_table,
+                            const torch::Tensor& map_item,
+                            const torch::Tensor& map_pos0,
+                            const torch::Tensor& item_off,
+                            const torch::Tensor& item_start,
+                            const torch::Tensor& item_len) {
+  chk_same_gpu({{"q", q}, {"kc", kc}, {"vc", vc},
+                {"block_table", block_table}, {"item map", map_item},
+                {"pos0 map", map_pos0}, {"item_off", item_off},
+                {"item_start", item_start}, {"item_len", item_len}});
+  const int D = chk_heads(q, "q");
+  chk_rows16(q, "q");
+  TORCH_CHECK(kc.dim() == 5, "K cache layout [P, KVH, D/8, 64, 8]");
+  const int KVH = kc.size(1);
+  chk_gqa(q.size(1), KVH);
+  chk_kv_cache(kc, vc, KVH, D);
+  const long nb = item_len.numel();
+  chk_index(item_off, nb, "item_off");
+  chk_index(item_start, nb, "item_start");
+  chk_index(item_len, nb, "item_len");
+  chk_block_table(block_table, nb);
+  chk_index(map_item, map_item.numel(), "item map");
+  chk_index(map_pos0, map_item.numel(), "pos0 map");
+  return D;
 }
 
 torch::Tensor paged_attn_prefill(torch::Tensor q, torch::Tensor kc,
@@ -370,20 +484,16 @@ torch::Tensor paged_attn_prefill(torch::Tensor q, torch::Tensor kc,
                                  torch::Tensor item_start,
                                  torch::Tensor item_len, double scale,
                                  bool causal) {
-  CHK_DEV(q); CHK_BF16(q); CHK_BF16(kc); CHK_BF16(vc);
-  CHK_CONT(kc); CHK_CONT(vc); CHK_I32(block_table); CHK_CONT(block_table);
-  CHK_I32(qb_item); CHK_I32(qb_pos0); CHK_I32(item_off);
-  CHK_I32(item_start); CHK_I32(item_len);
-  const int T = q.size(0), QH = q.size(1), D = q.size(2);
-  chk_hd_strided(q, D, "q");
-  const int KVH = kc.size(1);
-  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
-  TORCH_CHECK(QH % KVH == 0 && QH / KVH <= 16, "GQA ratio <= 16");
+  const int QB = qb_item.numel();
+  const int D = chk_prefill_args(q, kc, vc, block_table, qb_item, qb_pos0,
+                                 item_off, item_start, item_len);
+  const int T = q.size(0), QH = q.size(1), KVH = kc.size(1);
   TORCH_CHECK(QH % 4 == 0, "QH % 4 == 0 (4 head-waves per workgroup "
               "lockstep on a shared page stream)");
-  TORCH_CHECK(vc.size(2) == D && vc.size(3) == 64, "V layout [P,KVH,D,64]");
-  const int QB = qb_item.numel();
   const int npmax = block_table.size(1);
+  // no block, no launch: rows that no block covers read as zero
+  if (QB == 0 || T == 0)
+    return torch::zeros({(long long)T, (long long)QH * D}, q.options());
   auto out = torch::empty({(long long)T, (long long)QH * D}, q.options());
   qsa_paged_attn_prefill_launch(
       u16(q), u16(kc), u16(vc), block_table.data_ptr<int>(),
@@ -404,27 +514,16 @@ torch::Tensor paged_attn_prefill_tiled(
     torch::Tensor block_table, torch::Tensor tile_item,
     torch::Tensor tile_pos0, torch::Tensor item_off, torch::Tensor item_start,
     torch::Tensor item_len, double scale, bool causal, long rows) {
-  CHK_DEV(q); CHK_BF16(q); CHK_BF16(kc); CHK_BF16(vc);
-  CHK_CONT(kc); CHK_CONT(vc); CHK_I32(block_table); CHK_CONT(block_table);
-  CHK_I32(tile_item); CHK_I32(tile_pos0); CHK_I32(item_off);
-  CHK_I32(item_start); CHK_I32(item_len);
-  CHK_CONT(tile_item); CHK_CONT(tile_pos0);
-  const int T = q.size(0), QH = q.size(1), D = q.size(2);
-  chk_hd_strided(q, D, "q");
-  const int KVH = kc.size(1);
-  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
+  const int NT = tile_item.numel();
+  const int D = chk_prefill_args(q, kc, vc, block_table, tile_item, tile_pos0,
+                                 item_off, item_start, item_len);
+  const int T = q.size(0), QH = q.size(1), KVH = kc.size(1);
   TORCH_CHECK(rows == 32 || (rows == 64 && D == 64),
               "rows must be 32 (or 64 at D == 64)");
-  TORCH_CHECK(QH % KVH == 0 && QH / KVH <= 16, "GQA ratio <= 16");
-  TORCH_CHECK(q.stride(0) % 8 == 0 &&
-              reinterpret_cast<uintptr_t>(q.data_ptr()) % 16 == 0,
-              "q rows must be 16-byte aligned");
-  TORCH_CHECK(kc.size(2) == D / 8 && kc.size(3) == 64 && kc.size(4) == 8,
-              "K cache layout [P, KVH, D/8, 64, 8]");
-  TORCH_CHECK(vc.size(2) == D && vc.size(3) == 64, "V layout [P,KVH,D,64]");
-  TORCH_CHECK(tile_item.numel() == tile_pos0.numel(), "tile maps");
-  const int NT = tile_item.numel();
   const int npmax = block_table.size(1);
+  // no tile, no launch, on the tiled path and on the fallback alike
+  if (NT == 0 || T == 0)
+    return torch::zeros({(long long)T, (long long)QH * D}, q.options());
   auto out = torch::empty({(long long)T, (long long)QH * D}, q.options());
   const int done = qsa_paged_attn_prefill_tiled_launch(
       u16(q), u16(kc), u16(vc), block_table.data_ptr<int>(),
@@ -449,32 +548,23 @@ void rope_kv_scatter(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                      torch::Tensor kc, torch::Tensor vc, torch::Tensor cos_t,
                      torch::Tensor sin_t, torch::Tensor pos,
                      torch::Tensor slots) {
-  CHK_DEV(q); CHK_BF16(q); CHK_BF16(k); CHK_BF16(v); CHK_BF16(kc);
-  CHK_BF16(vc); CHK_CONT(kc); CHK_CONT(vc);
-  CHK_F32(cos_t); CHK_F32(sin_t); CHK_CONT(cos_t); CHK_CONT(sin_t);
-  CHK_I32(pos); CHK_I32(slots); CHK_CONT(pos); CHK_CONT(slots);
-  const int Tq = q.size(0), QH = q.size(1), D = q.size(2);
+  chk_same_gpu({{"q", q}, {"k", k}, {"v", v}, {"kc", kc}, {"vc", vc},
+                {"cos_t", cos_t}, {"sin_t", sin_t}, {"pos", pos},
+                {"slots", slots}});
+  const int D = chk_heads(q, "q");
+  const int Tq = q.size(0), QH = q.size(1);
+  TORCH_CHECK(k.dim() == 3 && v.dim() == 3 && k.size(0) == v.size(0),
+              "k/v must be [rows, KVH, D]");
   const int KVH = k.size(1);
   const int T = slots.numel();
-  TORCH_CHECK(D == 128 || D == 64, "D must be 64/128");
-  chk_hd_strided(q, D, "q"); chk_hd_strided(k, D, "k");
-  chk_hd_strided(v, D, "v");
-  TORCH_CHECK(k.size(2) == D && v.size(2) == D && v.size(1) == KVH,
-              "k/v shape");
-  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v strides must match");
-  TORCH_CHECK(pos.numel() == Tq, "one position per q row");
-  TORCH_CHECK(T <= Tq && T <= k.size(0) && T <= v.size(0),
-              "slots longer than q/k/v");
-  TORCH_CHECK(kc.size(1) == KVH && kc.size(2) == D / 8 && kc.size(3) == 64 &&
-              kc.size(4) == 8, "K cache layout [P, KVH, D/8, 64, 8]");
-  TORCH_CHECK(vc.size(1) == KVH && vc.size(2) == D && vc.size(3) == 64,
-              "V cache layout [P, KVH, D, 64]");
-  auto al16 = [](const torch::Tensor& t) {
-    return reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0;
-  };
-  TORCH_CHECK(q.stride(0) % 8 == 0 && k.stride(0) % 8 == 0 && al16(q) &&
-              al16(k) && al16(v) && al16(kc) && al16(cos_t) && al16(sin_t),
-              "rope_kv_scatter needs 16-byte aligned rows");
+  chk_kv_rows(k, v, k.size(0), KVH, D);
+  chk_index(pos, Tq, "pos");
+  chk_index(slots, T, "slots");
+  TORCH_CHECK(T <= Tq && T <= k.size(0), "slots longer than q/k/v");
+  chk_kv_cache(kc, vc, KVH, D);
+  chk_rope_tables(cos_t, sin_t, D);
+  // 16-byte loads of q, k and v rows
+  chk_rows16(q, "q"); chk_rows16(k, "k"); chk_rows16(v, "v");
   if (Tq == 0) return;
   qsa_rope_kv_scatter_launch(u16m(q), u16(k), u16(v), u16m(kc), u16m(vc),
                              cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
@@ -487,14 +577,19 @@ void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                     torch::Tensor kc, torch::Tensor vc, torch::Tensor cos_t,
                     torch::Tensor sin_t, torch::Tensor block_table,
                     torch::Tensor seq_lens) {
-  CHK_DEV(q); CHK_BF16(q); CHK_BF16(k); CHK_BF16(v);
-  CHK_F32(cos_t); CHK_F32(sin_t); CHK_I32(block_table); CHK_I32(seq_lens);
-  CHK_CONT(block_table);
-  const int B = q.size(0), QH = q.size(1), D = q.size(2);
+  chk_same_gpu({{"q", q}, {"k", k}, {"v", v}, {"kc", kc}, {"vc", vc},
+                {"cos_t", cos_t}, {"sin_t", sin_t},
+                {"block_table", block_table}, {"seq_lens", seq_lens}});
+  const int D = chk_heads(q, "q");
+  const int B = q.size(0), QH = q.size(1);
+  TORCH_CHECK(k.dim() == 3, "k/v must be [rows, KVH, D]");
   const int KVH = k.size(1);
-  chk_hd_strided(q, D, "q"); chk_hd_strided(k, D, "k");
-  chk_hd_strided(v, D, "v");
-  TORCH_CHECK(k.stride(0) == v.stride(0), "k/v strides must match");
+  chk_kv_rows(k, v, B, KVH, D);
+  chk_kv_cache(kc, vc, KVH, D);
+  chk_rope_tables(cos_t, sin_t, D);
+  chk_block_table(block_table, B);
+  chk_index(seq_lens, B, "seq_lens");
+  if (B == 0 || QH + KVH == 0) return;
   qsa_rope_kv_append_launch(u16m(q), u16(k), u16(v), u16m(kc), u16m(vc),
                             cos_t.data_ptr<float>(), sin_t.data_ptr<float>(),
                             block_table.data_ptr<int>(),
@@ -505,11 +600,14 @@ void rope_kv_append(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 
 void kv_scatter(torch::Tensor knew, torch::Tensor vnew, torch::Tensor kc,
                 torch::Tensor vc, torch::Tensor slots) {
-  CHK_DEV(knew); CHK_BF16(knew); CHK_BF16(vnew); CHK_I32(slots);
-  const int T = knew.size(0), KVH = knew.size(1), D = knew.size(2);
-  chk_hd_strided(knew, D, "knew"); chk_hd_strided(vnew, D, "vnew");
-  TORCH_CHECK(knew.stride(0) == vnew.stride(0), "k/v strides must match");
-  if (T == 0) return;
+  chk_same_gpu({{"knew", knew}, {"vnew", vnew}, {"kc", kc}, {"vc", vc},
+                {"slots", slots}});
+  const int D = chk_heads(knew, "knew");
+  const int T = knew.size(0), KVH = knew.size(1);
+  chk_kv_rows(knew, vnew, T, KVH, D);
+  chk_kv_cache(kc, vc, KVH, D);
+  chk_index(slots, T, "slots");
+  if (T == 0 || KVH == 0) return;
   qsa_kv_scatter_launch(u16(knew), u16(vnew), u16m(kc), u16m(vc),
                         slots.data_ptr<int>(), T, KVH, D, knew.stride(0),
                         cur_stream());
