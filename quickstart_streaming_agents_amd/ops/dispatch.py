@@ -468,14 +468,19 @@ def greedy_sample_step(logits: torch.Tensor, lo: int, hi: int, eos: int,
 # ops/hip/sampling.hip, agrees with it bit for bit).  Per row: bf16
 # logits[V]; the window lo, hi, eos of greedy_sample_step; inv_temp (f32);
 # top_k (i32, 0 = off); top_p_q (i32 in [1, 65536], 65536 = off); seed (64
-# bits); pos (i32).  A row's token depends on these alone.
+# bits); pos (i32).  A row's token depends on these alone.  inv_temp must be
+# finite and >= 0 (SamplingParams guarantees it; the ops cannot check a
+# device tensor), and the claim is for NaN-free logits, as for
+# greedy_sample_step.
 #
 # Candidates: the indices in [lo, hi) U {eos}, in ascending index order.
 # Greedy rows: inv_temp == 0 gives the greedy_sample_step token, the
 #   lowest-index argmax over the candidates (0 if all are -inf); the other
 #   parameters are ignored.
-# Weight: m = the maximum candidate logit; m == -inf gives token 0.  In f32,
-#   every operation rounded on its own (no FMA):
+# Weight: m = the maximum candidate logit; m == -inf gives token 0 and
+#   m == +inf gives the greedy token, the lowest-index +inf candidate (no
+#   weight is defined against an infinite maximum).  In f32, every operation
+#   rounded on its own (no FMA):
 #     d = l - m;  x = d * inv_temp;  y = max(x * LOG2E, -64)
 #     n = floor(y + 0.5);  f = y - n
 #     p = Horner(f), coefficients c_k = f32(ln2^k / k!), k = 6..0: the
@@ -483,8 +488,10 @@ def greedy_sample_step(logits: torch.Tensor, lo: int, hi: int, eos: int,
 #         most (ln2/2)^7/7! ~ 1.2e-7
 #     q = (u32) trunc(p * 2^24)
 #     w = ((u64) q << 16) >> (-n) when -n <= 40, else 0
-#   The maximum has w = 2^40, totals stay below 2^58, and a token below
-#   2^-40 of the maximum has weight 0 and is never drawn.
+#   The maximum has w = 2^40, so totals stay below 2^40 times the number of
+#   candidates: below 2^58 up to 2^18 candidates, below 2^62 at the largest
+#   V the kernel takes (2046 * 2048), inside 64 bits either way.  A token
+#   below 2^-40 of the maximum has weight 0 and is never drawn.
 # Key: the order-preserving 16-bit key of the bf16 logit.  The weight
 #   depends on the logit alone, so thresholds are thresholds on the key.
 # top-k: tau_k = the largest key with count(key >= tau_k) >= top_k, the
@@ -586,7 +593,8 @@ def _sample_rows_cpu(logits, lo, hi, eos, inv_temp, top_k, top_p_q, seed,
     greedy = cand[(lf == m[:, None]).int().argmax(dim=1)]
     greedy = torch.where(dead, torch.zeros_like(greedy), greedy)
     inv_temp = inv_temp[:B].float()
-    sampled = (inv_temp != 0) & ~dead
+    # a +inf maximum keeps the greedy token: no weight is defined against it
+    sampled = (inv_temp != 0) & ~dead & (m != float("inf"))
     if not bool(sampled.any()):
         return greedy
     rows = sampled.nonzero(as_tuple=True)[0]

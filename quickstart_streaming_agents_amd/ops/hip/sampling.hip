@@ -15,8 +15,9 @@
 // threshold falls in the same high-byte bin); a blocked final pass that
 // sums the kept weights per block of 2048 candidates, which gives the total
 // and hence the drawn target, and scans by candidate only the block where
-// the running sum passes it.  A row with inv_temp == 0 leaves after the max pass
-// with the greedy kernel's token (elementwise.hip).  The bookkeeping
+// the running sum passes it.  A row with inv_temp == 0, or whose maximum is
+// +inf or -inf, leaves after the max pass with the greedy kernel's token
+// (elementwise.hip).  NaN logits are outside the claim, as there.  The bookkeeping
 // (script override, hist, tokens, ticketed ctr += 1) is the greedy
 // kernel's.
 #include "common.h"
@@ -260,9 +261,11 @@ qsa_sample_kernel(const unsigned short* __restrict__ logits,     // [B,V]
   bv = sv[0]; bi = si[0];
   for (int w = 1; w < 4; ++w) qsa_argmax_take(bv, bi, sv[w], si[w]);
 
-  int tok = bi;                 // greedy rows; 0 when every candidate is -inf
+  // greedy rows; 0 when every candidate is -inf; the lowest-index +inf
+  // when the maximum is +inf (no weight is defined against it)
+  int tok = bi;
   const float it = inv_temp[row];
-  if (it != 0.f && bv != ninf) {          // block-uniform
+  if (it != 0.f && bv != ninf && bv != -ninf) {     // block-uniform
     const float m = bv;
     const int k = top_k[row];
     const int pq = top_p_q[row];
