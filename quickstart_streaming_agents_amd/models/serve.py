@@ -31,6 +31,8 @@ so they do not depend on batch mates, ladder rung, run length or TP rank.
 
 from __future__ import annotations
 
+import contextlib
+import gc
 import math
 import random
 import time
@@ -39,6 +41,23 @@ from dataclasses import dataclass, field
 import torch
 
 from .llama import LlamaModel
+
+
+@contextlib.contextmanager
+def _gc_quiet():
+    """Collect dead cycles now and keep the cyclic collector off inside.
+    An Engine is a cycle (it holds its graph body, which holds it), so a
+    dropped one dies only when the collector runs; if that happens while a
+    stream is capturing, the destructors of its CUDAGraphs synchronise the
+    device, which a capture does not allow, and the process aborts."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 @dataclass(frozen=True)
@@ -453,20 +472,22 @@ class Engine:
         same memory pool."""
         gb, body = self._gbuf, self._graph_body
         graphs: dict = {}
-        for b in reversed(self._rungs):   # largest first: it sizes the pool
-            # warm up the exact captured ops (allocator + rocBLAS algo
-            # selection)
-            for _ in range(2):
-                body(b, sampled)
-            gb["ctr"].zero_()
-            gb["seq_lens"].zero_()
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=self._graph_pool):
-                body(b, sampled)
-            if self._graph_pool is None:
-                self._graph_pool = g.pool()
-            graphs[b] = g
+        with _gc_quiet():
+            # largest first: it sizes the pool
+            for b in reversed(self._rungs):
+                # warm up the exact captured ops (allocator + rocBLAS algo
+                # selection)
+                for _ in range(2):
+                    body(b, sampled)
+                gb["ctr"].zero_()
+                gb["seq_lens"].zero_()
+                torch.cuda.synchronize()
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g, pool=self._graph_pool):
+                    body(b, sampled)
+                if self._graph_pool is None:
+                    self._graph_pool = g.pool()
+                graphs[b] = g
         return graphs
 
     def _ensure_sampled_graph(self) -> bool:

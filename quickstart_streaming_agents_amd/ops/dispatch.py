@@ -352,9 +352,13 @@ def moe_dispatch(h: torch.Tensor, top_idx: torch.Tensor, n_experts: int,
 
 
 def _moe_grouped(xg, counts, n, fn):
-    out = torch.zeros(xg.shape[0], xg.shape[1], n, dtype=xg.dtype,
-                      device=xg.device)
+    """out[e, :c] = fn(e, xg[e, :c]) with c = counts[e] clamped to
+    [0, cap], as the kernels clamp it: a negative count is an expert
+    without rows, a count above cap is cap."""
+    cap = xg.shape[1]
+    out = torch.zeros(xg.shape[0], cap, n, dtype=xg.dtype, device=xg.device)
     for e, c in enumerate(counts.tolist()):
+        c = min(c, cap)
         if c > 0:
             out[e, :c] = fn(e, xg[e, :c])
     return out
@@ -398,15 +402,17 @@ def moe_combine(y: torch.Tensor, slot: torch.Tensor, top_idx: torch.Tensor,
     in ascending expert index, in f32 from zero with the multiply and the
     add rounded separately (no FMA), rounded once to y's dtype: the
     arithmetic of the dense masked sum over all experts.  Dead picks
-    (slot < 0) add nothing, so a dead row gives zeros."""
+    (a slot outside [0, cap) or an expert outside [0, E)) add nothing, so
+    a dead row gives zeros."""
     if y.is_cuda:
         return ext().moe_combine(y, slot, top_idx, top_w)
     T, k = top_idx.shape
+    cap = y.shape[1]
     out = torch.zeros(T, y.shape[2], dtype=torch.float32)
     for e in range(y.shape[0]):
         for j in range(k):
-            rows = ((top_idx[:, j] == e) & (slot[:, j] >= 0)) \
-                .nonzero(as_tuple=True)[0]
+            rows = ((top_idx[:, j] == e) & (slot[:, j] >= 0) &
+                    (slot[:, j] < cap)).nonzero(as_tuple=True)[0]
             if rows.numel() == 0:
                 continue
             prod = top_w[rows, j].float().unsqueeze(1) * \

@@ -197,30 +197,35 @@ def _seed(*key):
 
 
 @functools.lru_cache(maxsize=None)
-def int_fp8_case(N, K, rows):
+def int_fp8_case(N, K, rows, variant=0):
     """Integer fp8 case: a [rows, K] bf16, packed weights, scales and the
-    integer codes.  The exactness of the pack is asserted here."""
-    g = _gen(_seed(1, N, K))
+    integer codes.  The exactness of the pack is asserted here.  variant
+    > 0: other data of the same recipe (one per expert of a grouped
+    case)."""
+    g = _gen(_seed(1, N, K) if variant == 0 else _seed(1, N, K, variant))
     a = torch.randint(-4, 5, (rows, K), generator=g).bfloat16()
     q = torch.randint(-8, 9, (N, K), generator=g).to(torch.int16)
     col = torch.randint(0, K, (N,), generator=g)
     sign = torch.randint(0, 2, (N,), generator=g).to(torch.int16) * 2 - 1
     q[torch.arange(N), col] = 448 * sign
     s = channel_scales(N)
+    if variant:         # another power-of-two pattern per variant
+        s = torch.roll(s, variant % 8) * 2.0 ** -(variant // 8)
     qf, _ = fp8_weight(q.float(), s)
     return types.SimpleNamespace(kind="fp8", N=N, K=K, a=a, qf=qf, s=s, q=q,
                                  refs={})
 
 
 @functools.lru_cache(maxsize=None)
-def int_bf16_case(N, K, rows):
-    """Integer bf16 case.  Uniform integers alone leave most outputs below
+def int_bf16_case(N, K, rows, variant=0):
+    """Integer bf16 case (variant: as in int_fp8_case).
+    Uniform integers alone leave most outputs below
     256, where every integer is a bf16 number and the store rounds nothing
     (the fp8 cases have their +-448 for this).  So BF16_ALIGNED seeded
     columns hold a = p[k] * {3, 4} and w = c[n] * p[k] * {6, 7, 8} with
     seeded signs p, c: their products add up to about +-980 per output,
     which needs 10 or 11 bits."""
-    g = _gen(_seed(2, N, K))
+    g = _gen(_seed(2, N, K) if variant == 0 else _seed(2, N, K, variant))
     a = torch.randint(-4, 5, (rows, K), generator=g).to(torch.int16)
     q = torch.randint(-8, 9, (N, K), generator=g).to(torch.int16)
     cols = torch.randperm(K, generator=g)[:BF16_ALIGNED]

@@ -15,6 +15,8 @@ kernel must read what it appended), V slots there are finite because the
 kernels multiply them by P = 0.
 """
 
+import gc
+
 import pytest
 import torch
 
@@ -237,6 +239,7 @@ def test_fused_graph_replay_matches_eager_oracle(ext, D):
             body()      # all rows inactive: touches nothing
     torch.cuda.current_stream().wait_stream(s)
     torch.cuda.synchronize()
+    gc.collect()    # no dead Engine's graphs may be freed inside the capture
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         body()

@@ -4,6 +4,8 @@ Everything is exact: the oracles are the project's own single-expert kernels
 loop and the CPU references of test_moe_routed.py, so no tolerance is
 involved anywhere."""
 
+import gc
+
 import pytest
 import torch
 import torch.nn.functional as F
@@ -354,6 +356,7 @@ def test_graph_capture_follows_the_routing(models, fmt):
         with torch.cuda.stream(side):
             m._ffn(L, static_h)
         torch.cuda.current_stream().wait_stream(side)
+        gc.collect()    # no dead Engine's graphs may be freed in the capture
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             static_out = m._ffn(L, static_h)
