@@ -77,6 +77,17 @@ class PagedKVCache:
     def seq_len(self, seq_id: int) -> int:
         return self._seq_len.get(seq_id, 0)
 
+    def set_len(self, seq_id: int, n: int) -> None:
+        """Record that n positions of the sequence are in use; its pages
+        must already hold them."""
+        assert self.pages_for(n) <= len(self._seq_pages[seq_id]), \
+            f"{n} positions exceed the pages of sequence {seq_id}"
+        self._seq_len[seq_id] = n
+
+    def pages(self, seq_id: int) -> list[int]:
+        """The sequence's page list, in position order."""
+        return self._seq_pages[seq_id]
+
     # ---- tensors for a step ---------------------------------------------
     def block_table(self, seq_ids: list[int]) -> torch.Tensor:
         max_pages = max(len(self._seq_pages[s]) for s in seq_ids)

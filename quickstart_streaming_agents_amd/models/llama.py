@@ -433,7 +433,7 @@ class LlamaModel:
             len_t = torch.tensor(lens, dtype=torch.int32, device=dev)
             bt = torch.zeros(nb, npmax, dtype=torch.int32)
             for i, (_, sid, _) in enumerate(items):
-                pages = kv._seq_pages[sid]
+                pages = kv.pages(sid)
                 bt[i, :len(pages)] = torch.tensor(pages, dtype=torch.int32)
             bt_t = bt.to(dev)
         else:
@@ -445,7 +445,7 @@ class LlamaModel:
                 dtype=torch.int64, device=dev)
             page_idx = torch.zeros(nb, npmax, dtype=torch.int64)
             for i, (_, sid, _) in enumerate(items):
-                pages = kv._seq_pages[sid]
+                pages = kv.pages(sid)
                 page_idx[i, :len(pages)] = torch.tensor(pages,
                                                         dtype=torch.int64)
             flat_pages = page_idx.reshape(-1).to(dev)

@@ -15,8 +15,9 @@ sequence alive between turns, the engine rolls the cache back to the shared
 prompt prefix and prefills only the delta (observation text) — turn N of an
 episode costs O(new tokens), not O(whole transcript).
 
-The decode step is hipGraph-captured at a ladder of row counts (16, 32, 64,
-max_batch) and each run replays the smallest rung that holds its live rows,
+The decode step (models/decode_graph.py, DecodeGraphs.step) is
+hipGraph-captured at a ladder of row counts (16, 32, 64, max_batch) and
+each run replays the smallest rung that holds its live rows,
 so a nearly drained batch pays for its own rows, not for max_batch
 (QSA_DECODE_LADDER=0: one max_batch graph).
 
@@ -31,33 +32,17 @@ so they do not depend on batch mates, ladder rung, run length or TP rank.
 
 from __future__ import annotations
 
-import contextlib
-import gc
 import math
+import os as _os
 import random
 import time
 from dataclasses import dataclass, field
 
 import torch
 
+from .decode_graph import (_TIMING, DecodeGraphs, TokenPolicy,  # noqa: F401
+                           _seed_i64, pick_rung)
 from .llama import LlamaModel
-
-
-@contextlib.contextmanager
-def _gc_quiet():
-    """Collect dead cycles now and keep the cyclic collector off inside.
-    An Engine is a cycle (it holds its graph body, which holds it), so a
-    dropped one dies only when the collector runs; if that happens while a
-    stream is capturing, the destructors of its CUDAGraphs synchronise the
-    device, which a capture does not allow, and the process aborts."""
-    gc.collect()
-    was_enabled = gc.isenabled()
-    gc.disable()
-    try:
-        yield
-    finally:
-        if was_enabled:
-            gc.enable()
 
 
 @dataclass(frozen=True)
@@ -94,11 +79,6 @@ class SamplingParams:
     def top_p_q(self) -> int:
         """top_p in 16-bit fixed point, 65536 = off."""
         return min(65536, max(1, int(self.top_p * 65536 + 0.5)))
-
-
-def _seed_i64(seed: int) -> int:
-    """The 64 seed bits as the two's-complement value an i64 tensor holds."""
-    return seed - (1 << 64) if seed >= 1 << 63 else seed
 
 
 @dataclass
@@ -150,8 +130,6 @@ class EngineStats:
         default_factory=lambda: {"greedy": 0, "sampled": 0})
 
 
-import os as _os
-_TIMING = _os.environ.get("QSA_TIMING", "") == "1"
 _TUNABLE_DONE = False
 # QSA_DECODE_LADDER=0 (read once, here) restores the single max_batch decode
 # graph for A/B runs; tests flip the module attribute.
@@ -168,14 +146,6 @@ def ladder_rungs(max_batch: int, ladder: bool = True) -> tuple:
     if not ladder:
         return (max_batch,)
     return tuple(c for c in LADDER_CANDIDATES if c < max_batch) + (max_batch,)
-
-
-def pick_rung(rungs: tuple, n: int) -> int:
-    """Smallest rung that holds n live rows (rungs ascending)."""
-    for r in rungs:
-        if r >= n:
-            return r
-    raise ValueError(f"{n} live rows exceed the largest rung {rungs[-1]}")
 
 
 def _enable_tunableop() -> None:
@@ -212,11 +182,6 @@ class Engine:
         self.model = model
         # seeds of requests whose SamplingParams leave the seed open
         self._seed_rng = random.Random(seed)
-        # temperature 0 = greedy (the deterministic benchmark contract);
-        # > 0 samples via the Gumbel-argmax trick, which stays a single
-        # argmax and is hipGraph-capture-safe (torch captures RNG state
-        # advancement, so replays draw fresh noise)
-        self.temperature = float(temperature)
         # grammar decision tokens are SAMPLED from the model's masked
         # distribution (temperature-1 Gumbel-argmax by default): the
         # model's logits drive tool-vs-finish control flow, as in real
@@ -255,48 +220,14 @@ class Engine:
         # nothing (every decoded token reads back as 0).
         self.use_graph = torch.cuda.is_available() and \
             torch.device(model.device).type == "cuda"
-        self._graph = None       # the max_batch rung's graph
-        self._graphs: dict = {}  # rung (rows) -> captured graph
-        self._rungs: tuple = ()
-        self._graph_failed = False
-        self._gbuf: dict = {}
-        # the second ladder (per-request sampler), captured on first need
-        self._graphs_sampled: dict = {}
-        self._sampled_failed = False
-        self._graph_pool = None
-        self._graph_body = None
-        # free-text sampling mask: tokens outside [lo, hi) (plus EOS) are
-        # never emitted — keeps random-init decode inside the tokenizer's
-        # trained vocab so outputs are real text (models/grammar.py)
-        self._vocab_bias: torch.Tensor | None = None
-        self._valid_vocab = None
-        if valid_vocab is not None:
-            lo, hi = valid_vocab
-            self._valid_vocab = (int(lo), int(hi))
-            bias = torch.full((model.cfg.vocab_size,), float("-inf"),
-                              device=model.device, dtype=torch.float32)
-            bias[lo:hi] = 0.0
-            if self.eos_id is not None:
-                bias[self.eos_id] = 0.0
-            self._vocab_bias = bias
-
-    def _sample(self, logits: torch.Tensor) -> torch.Tensor:
-        """Greedy at temperature 0; Gumbel-argmax sampling otherwise."""
-        if self._vocab_bias is not None:
-            logits = logits.float() + self._vocab_bias
-        if self.temperature <= 0.0:
-            return torch.argmax(logits, dim=-1)
-        u = torch.rand(logits.shape, device=logits.device,
-                       dtype=torch.float32).clamp_min_(1e-20)
-        gumbel = -torch.log(-torch.log(u).clamp_min_(1e-20))
-        return torch.argmax(logits.float() + self.temperature * gumbel,
-                            dim=-1)
-
-    def _window(self, logits: torch.Tensor) -> tuple[int, int, int]:
-        """lo, hi, eos of the samplers: the valid-vocab window, or the
-        whole vocabulary without one."""
-        lo, hi = self._valid_vocab or (0, logits.shape[-1])
-        return lo, hi, -1 if self.eos_id is None else int(self.eos_id)
+        self.graphs: DecodeGraphs | None = None   # built on first use
+        # engine-wide token policy.  temperature 0 = greedy (the
+        # deterministic benchmark contract); > 0 samples via the
+        # Gumbel-argmax trick, which stays a single argmax and is
+        # hipGraph-capture-safe (torch captures RNG state advancement, so
+        # replays draw fresh noise)
+        self.policy = TokenPolicy(temperature, valid_vocab, eos_id,
+                                  model.cfg.vocab_size, model.device)
 
     def _sample_rows(self, logits: torch.Tensor, seqs: list["Sequence"],
                      pos: list[int]) -> list[int]:
@@ -308,7 +239,7 @@ class Engine:
         def col(vals, dtype):
             return torch.tensor(vals, dtype=dtype, device=dev)
 
-        lo, hi, eos = self._window(logits)
+        lo, hi, eos = self.policy.window(logits)
         toks = D.sample_tokens(
             logits.to(torch.bfloat16).contiguous(), lo, hi, eos,
             col([s.sampling.inv_temp for s in seqs], torch.float32),
@@ -337,7 +268,7 @@ class Engine:
                              admitted: list["Sequence"]) -> list[int]:
         """Sample each admitted sequence's first token, honoring per-row
         decision masks (grammar turns) with ONE host sync."""
-        free = self._sample(logits)
+        free = self.policy.sample(logits)
         rows = [i for i, s in enumerate(admitted) if s.decision_allowed]
         if not rows:
             return [int(t) for t in free.tolist()]
@@ -365,149 +296,26 @@ class Engine:
     # ---- hipGraph decode -------------------------------------------------
     MAX_RUN = 512  # on-device token-history depth per graph run
 
-    def _ensure_graph(self) -> bool:
-        if self._graph is not None:
+    def _ensure_graphs(self) -> bool:
+        """Build the DecodeGraphs and capture the greedy ladder on first
+        use."""
+        if self.graphs is not None:
             return True
-        if self._graph_failed:
+        if not self.use_graph:
             return False
         try:
-            self._capture_graph()
+            graphs = DecodeGraphs(
+                self.model, self.kv, self.policy, self.max_batch,
+                self.max_seq_len, self.MAX_RUN,
+                ladder_rungs(self.max_batch, DECODE_LADDER))
+            graphs.capture(sampled=False)
+            self.graphs = graphs
             return True
         except Exception:
             # capture failed (e.g. an op that refuses stream capture on
             # this stack): permanent eager fallback, correctness first
-            self._graph_failed = True
             self.use_graph = False
-            self._graph = None
-            self._graphs = {}
-            torch.cuda.synchronize()
-            return False
-
-    def _fused_sampler(self, logits: torch.Tensor) -> bool:
-        """The one-launch greedy sampler (ops/hip/elementwise.hip) applies
-        to greedy decoding of GPU bf16 logits under a vocab window."""
-        return self.temperature <= 0.0 and self._valid_vocab is not None \
-            and logits.is_cuda and logits.dtype == torch.bfloat16
-
-    def _capture_graph(self) -> None:
-        """Capture the decode step once per ladder rung.  Every rung works
-        on the leading rows of the same max_batch buffers and all rungs
-        share one memory pool (they never replay concurrently), so a small
-        rung costs its kernels, not its own activations."""
-        from ..ops import dispatch as D
-        dev = self.model.device
-        B = self.max_batch
-        cap = (self.max_seq_len + 63) // 64
-        gb = {
-            "tokens": torch.zeros(B, dtype=torch.int64, device=dev),
-            "block_table": torch.zeros(B, cap, dtype=torch.int32, device=dev),
-            "seq_lens": torch.zeros(B, dtype=torch.int32, device=dev),
-            "active": torch.zeros(B, dtype=torch.int32, device=dev),
-            "ctr": torch.zeros(1, dtype=torch.int64, device=dev),
-            "hist": torch.zeros(self.MAX_RUN, B, dtype=torch.int64, device=dev),
-            # grammar scripts: forced token at run-step j for each row
-            # (script_mask False -> free sample)
-            "script": torch.zeros(B, self.MAX_RUN, dtype=torch.int64,
-                                  device=dev),
-            "script_mask": torch.zeros(B, self.MAX_RUN, dtype=torch.bool,
-                                       device=dev),
-            # scratch of the fused sampler kernel
-            "ticket": torch.zeros(1, dtype=torch.int32, device=dev),
-            # per-request sampling parameters (inv_temp 0: a greedy row)
-            "inv_temp": torch.zeros(B, dtype=torch.float32, device=dev),
-            "top_k": torch.zeros(B, dtype=torch.int32, device=dev),
-            "top_p_q": torch.full((B,), 65536, dtype=torch.int32,
-                                  device=dev),
-            "seed": torch.zeros(B, dtype=torch.int64, device=dev),
-        }
-        eos = -1 if self.eos_id is None else int(self.eos_id)
-
-        def body(b: int, sampled: bool = False):
-            # self-feeding decode step on rows [0, b): advance seq_lens
-            # in-graph, append the step's k/v at seq_lens-1, attend, sample,
-            # record, feed back.  forward_decode derives positions from
-            # seq_lens itself; its `positions` argument is unused.
-            tokens, seq_lens = gb["tokens"][:b], gb["seq_lens"][:b]
-            seq_lens.add_(gb["active"][:b])
-            logits = self.model.forward_decode(
-                tokens, self.kv, gb["block_table"][:b], seq_lens, None)
-            if sampled:
-                # the second ladder: every row through the per-request
-                # sampler, drawn at its absolute position (seq_lens after
-                # the add_)
-                lo, hi, _ = self._window(logits)
-                D.sample_step(
-                    logits.to(torch.bfloat16), lo, hi, eos,
-                    gb["inv_temp"][:b], gb["top_k"][:b], gb["top_p_q"][:b],
-                    gb["seed"][:b], seq_lens, gb["script"][:b],
-                    gb["script_mask"][:b], gb["ctr"], gb["hist"][:, :b],
-                    tokens, gb["ticket"])
-                return
-            if self._fused_sampler(logits):
-                lo, hi = self._valid_vocab
-                D.greedy_sample_step(
-                    logits, lo, hi, eos, gb["script"][:b],
-                    gb["script_mask"][:b], gb["ctr"], gb["hist"][:, :b],
-                    tokens, gb["ticket"])
-                return
-            nxt = self._sample(logits)
-            # grammar-forced tokens override the free sample in-graph
-            j = gb["ctr"].clamp(max=self.MAX_RUN - 1)
-            forced = gb["script"][:b].index_select(1, j).squeeze(1)
-            fmask = gb["script_mask"][:b].index_select(1, j).squeeze(1)
-            nxt = torch.where(fmask, forced, nxt)
-            gb["hist"][:, :b].index_copy_(0, gb["ctr"], nxt.unsqueeze(0))
-            gb["ctr"].add_(1)
-            tokens.copy_(nxt)
-
-        self._rungs = ladder_rungs(B, DECODE_LADDER)
-        self._gbuf = gb
-        self._graph_body = body
-        self._graph_pool = None
-        self._graphs = self._capture_ladder(sampled=False)
-        self._graph = self._graphs[B]
-
-    def _capture_ladder(self, sampled: bool) -> dict:
-        """One graph of the decode step per rung; both ladders draw on the
-        same memory pool."""
-        gb, body = self._gbuf, self._graph_body
-        graphs: dict = {}
-        with _gc_quiet():
-            # largest first: it sizes the pool
-            for b in reversed(self._rungs):
-                # warm up the exact captured ops (allocator + rocBLAS algo
-                # selection)
-                for _ in range(2):
-                    body(b, sampled)
-                gb["ctr"].zero_()
-                gb["seq_lens"].zero_()
-                torch.cuda.synchronize()
-                g = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g, pool=self._graph_pool):
-                    body(b, sampled)
-                if self._graph_pool is None:
-                    self._graph_pool = g.pool()
-                graphs[b] = g
-        return graphs
-
-    def _ensure_sampled_graph(self) -> bool:
-        """Capture the second ladder, whose sampler is the per-request
-        kernel, the first time a run needs it.  The graph buffers are idle
-        here (no live row), so the warm-up steps write nothing into the KV
-        cache."""
-        if self._graphs_sampled:
-            return True
-        if self._sampled_failed:
-            return False
-        self._gbuf["active"].zero_()
-        self._gbuf["seq_lens"].zero_()
-        try:
-            self._graphs_sampled = self._capture_ladder(sampled=True)
-            return True
-        except Exception:
-            # as _ensure_graph: runs with sampled rows go eager from here on
-            self._sampled_failed = True
-            self._graphs_sampled = {}
+            self.graphs = None
             torch.cuda.synchronize()
             return False
 
@@ -535,14 +343,15 @@ class Engine:
                                            positions)
         own = [i for i, s in enumerate(batch) if s.sampling is not None]
         if not own:
-            nxt = self._sample(logits).tolist()
+            nxt = self.policy.sample(logits).tolist()
         else:
             # rows that have `sampling` draw their own tokens, at the
             # position of the token being drawn; the rest as ever
             nxt = [0] * len(batch)
             rest = [i for i, s in enumerate(batch) if s.sampling is None]
             if rest:
-                for i, t in zip(rest, self._sample(logits[rest]).tolist()):
+                for i, t in zip(
+                        rest, self.policy.sample(logits[rest]).tolist()):
                     nxt[i] = t
             toks = self._sample_rows(
                 logits[own], [batch[i] for i in own],
@@ -559,12 +368,9 @@ class Engine:
                     tok = s.script[si]
             s.out_tokens.append(int(tok))
             self._maybe_finish(s)
-        self.stats.decode_tokens += len(batch)
-        self.stats.decode_steps += 1
-        by_live = self.stats.decode_steps_by_live
-        by_live[len(batch)] = by_live.get(len(batch), 0) + 1
-        which = "sampled" if any(s.sampled for s in batch) else "greedy"
-        self.stats.decode_steps_by_sampler[which] += 1
+        self._count_decode(
+            len(batch), 1,
+            "sampled" if any(s.sampled for s in batch) else "greedy")
 
     def _decode_run_graph(self, batch: list[Sequence], run: int) -> None:
         """Run `run` decode steps for `batch` with zero host round trips:
@@ -575,117 +381,44 @@ class Engine:
         draws.  (Under an engine-wide temperature above 0 the first
         ladder's policy is not greedy, so runs with `sampling` rows go
         eager there.)"""
-        if not self._ensure_graph():
+        if not self._ensure_graphs():
             self._decode_run_eager(batch, run)
             return
+        graphs = self.graphs
         sampled = any(s.sampled for s in batch)
-        if (sampled and not self._ensure_sampled_graph()) or (
-                self.temperature > 0.0
+        if sampled and not graphs.sampled and not graphs.sampled_failed:
+            graphs.capture(sampled=True)
+        if (sampled and not graphs.sampled) or (
+                self.policy.temperature > 0.0
                 and any(s.sampling is not None for s in batch)):
             self._decode_run_eager(batch, run)
             return
-        self._graph_run_begin(batch, run, sampled)
-        self._graph_run_end(batch, run)
-
-    def _graph_run_begin(self, batch: list[Sequence], run: int,
-                         sampled: bool = False) -> None:
-        """Fill the graph buffers and queue `run` replays (async on the
-        current stream — no host sync; _graph_run_end collects)."""
-        gb = self._gbuf
-        n = len(batch)
-        dev = self.model.device
-        for s in batch:  # pre-extend pages for the whole run
-            self.kv.extend(s.seq_id, len(s.prompt) + len(s.out_tokens) + run)
-            # seq_lens the graph starts from EXCLUDE the token the first
-            # replay decodes: the in-graph add_(active) then yields
-            # len(prompt)+len(out) for step 1 — the same "includes the
-            # new token" value the eager path passes (appending at slot
-            # len(prompt)+len(out)-1, no zero hole after the prompt)
-            self.kv._seq_len[s.seq_id] = \
-                len(s.prompt) + len(s.out_tokens) - 1
-        seq_ids = [s.seq_id for s in batch]
-        bt = self.kv.block_table(seq_ids)
-        gb["block_table"][:n, :bt.shape[1]] = bt
-        gb["seq_lens"][:n] = self.kv.seq_lens_tensor(seq_ids)
-        gb["tokens"][:n] = torch.tensor([s.out_tokens[-1] for s in batch],
-                                        dtype=torch.int64, device=dev)
-        gb["active"][:n] = 1
-        if n < self.max_batch:
-            gb["seq_lens"][n:] = 0
-            gb["active"][n:] = 0
-        # grammar scripts for this run window: run-step j emits
-        # out_tokens[d + j] whose script index is d - 1 + j (out_tokens[0]
-        # was the prefill-sampled decision token)
-        if any(s.script for s in batch):
-            sc = torch.zeros(n, run, dtype=torch.int64)
-            sm = torch.zeros(n, run, dtype=torch.bool)
-            for i, s in enumerate(batch):
-                if not s.script:
-                    continue
-                d = len(s.out_tokens)
-                window = s.script[d - 1: d - 1 + run]
-                if window:
-                    sc[i, :len(window)] = torch.tensor(window,
-                                                       dtype=torch.int64)
-                    sm[i, :len(window)] = True
-            gb["script"][:n, :run] = sc.to(dev)
-            gb["script_mask"][:n, :run] = sm.to(dev)
-            gb["script_mask"][:n, run:] = False
-            if n < self.max_batch:
-                gb["script_mask"][n:] = False
-        else:
-            gb["script_mask"].fill_(False)
-        gb["ctr"].zero_()
-        if sampled:
-            # rows without `sampling` (and the idle rows of the rung) are
-            # greedy rows of the per-request sampler
-            own = [s.sampling for s in batch]
-            gb["inv_temp"].zero_()
-            gb["inv_temp"][:n] = torch.tensor(
-                [p.inv_temp if p else 0.0 for p in own],
-                dtype=torch.float32, device=dev)
-            gb["top_k"][:n] = torch.tensor(
-                [p.top_k if p else 0 for p in own],
-                dtype=torch.int32, device=dev)
-            gb["top_p_q"][:n] = torch.tensor(
-                [p.top_p_q if p else 65536 for p in own],
-                dtype=torch.int32, device=dev)
-            gb["seed"][:n] = torch.tensor(
-                [_seed_i64(s.seed) if s.sampling else 0 for s in batch],
-                dtype=torch.int64, device=dev)
-        if _TIMING:
-            torch.cuda.synchronize()
-            self._t_graph0 = time.perf_counter()
-        # the rung depends on len(batch) alone, so the schedule and the
-        # results stay a deterministic function of the inputs
-        self._rung = pick_rung(self._rungs, n)
-        self._run_sampler = "sampled" if sampled else "greedy"
-        g = (self._graphs_sampled if sampled else self._graphs)[self._rung]
-        for _ in range(run):
-            g.replay()
-
-    def _graph_run_end(self, batch: list[Sequence], run: int) -> None:
-        gb = self._gbuf
-        n = len(batch)
-        if _TIMING:
-            torch.cuda.synchronize()
-            self.stats.decode_s += time.perf_counter() - self._t_graph0
-        hist = gb["hist"][:run, :n].t().tolist()  # one sync
+        hist, rung, dt = graphs.run(batch, run, sampled)
+        self.stats.decode_s += dt
         for s, toks in zip(batch, hist):
             new = [int(t) for t in toks]
             if self.eos_id is not None and self.eos_id in new:
                 # honor mid-run EOS: keep tokens up to and including it
                 new = new[: new.index(self.eos_id) + 1]
             s.out_tokens.extend(new)
-            self.kv._seq_len[s.seq_id] = len(s.prompt) + len(s.out_tokens)
+            self.kv.set_len(s.seq_id, len(s.prompt) + len(s.out_tokens))
             self._maybe_finish(s)
-        self.stats.decode_tokens += n * run
-        self.stats.decode_steps += run
-        by_live = self.stats.decode_steps_by_live
-        by_live[n] = by_live.get(n, 0) + run
-        by_rung = self.stats.decode_steps_by_rung
-        by_rung[self._rung] = by_rung.get(self._rung, 0) + run
-        self.stats.decode_steps_by_sampler[self._run_sampler] += run
+        self._count_decode(len(batch), run,
+                           "sampled" if sampled else "greedy", rung)
+
+    def _count_decode(self, live: int, steps: int, sampler: str,
+                      rung: int | None = None) -> None:
+        """Stats of `steps` decode steps with `live` rows (rung: the graph
+        rung that ran them, None for eager steps)."""
+        st = self.stats
+        st.decode_tokens += live * steps
+        st.decode_steps += steps
+        st.decode_steps_by_live[live] = \
+            st.decode_steps_by_live.get(live, 0) + steps
+        st.decode_steps_by_sampler[sampler] += steps
+        if rung is not None:
+            st.decode_steps_by_rung[rung] = \
+                st.decode_steps_by_rung.get(rung, 0) + steps
 
     # ------------------------------------------------------------------
     def submit(self, prompt_tokens: list[int], max_new_tokens: int,
@@ -765,8 +498,7 @@ class Engine:
         while self.pending and len(self.running) + len(admitted) < self.max_batch:
             seq = self.pending[0]
             total = len(seq.prompt) + seq.max_new_tokens
-            have = len(self.kv._seq_pages.get(seq.seq_id, ())) \
-                if seq.cached_len else 0
+            have = len(self.kv.pages(seq.seq_id)) if seq.cached_len else 0
             need = self.kv.pages_for(total) - have
             if need > self.kv.free_pages:
                 break
@@ -836,6 +568,15 @@ class Engine:
         self.finished.extend(done)
         self.running = [s for s in self.running if not s.done]
 
+    def _admit_all(self) -> None:
+        """Admit (possibly several prefill batches) until the pending queue
+        stops shrinking."""
+        while self.pending:
+            before = len(self.pending)
+            self._admit()
+            if len(self.pending) == before:
+                break
+
     def run_chunk(self, max_run: int = 16) -> int:
         """One continuous-batching slice: admit whatever fits, then up
         to `max_run` decode steps (one graph run).  Returns remaining
@@ -848,11 +589,7 @@ class Engine:
         # NON-deterministically at bench scale — the prefill's H2D /
         # allocator traffic races the replaying graph's memory pool on
         # this stack — so admissions and decode run sequentially.
-        while self.pending:
-            before = len(self.pending)
-            self._admit()
-            if len(self.pending) == before:
-                break
+        self._admit_all()
         batch = [s for s in self.running if not s.done]
         if batch:
             run = min(min(s.max_new_tokens - len(s.out_tokens)
@@ -864,8 +601,7 @@ class Engine:
                     self._decode_run_eager(batch, run)
         self._retire()
         if self.pending and not self.running and not batch:
-            raise MemoryError("decode stalled: pending prompts cannot be "
-                              "admitted (KV pages exhausted?)")
+            raise _stalled()
         return len(self.running) + len(self.pending)
 
     def step(self) -> int:
@@ -894,19 +630,13 @@ class Engine:
                 before = len(self.pending)
                 # drain the whole pending queue (possibly several prefill
                 # batches) before decoding: decode runs want the full batch
-                while self.pending:
-                    n_before = len(self.pending)
-                    self._admit()
-                    if len(self.pending) == n_before:
-                        break
+                self._admit_all()
                 batch = [s for s in self.running if not s.done]
                 if not batch:
                     self._retire()
                     if self.pending and len(self.pending) == before and \
                             not self.running:
-                        raise MemoryError(
-                            "decode stalled: pending prompts cannot be "
-                            "admitted (KV pages exhausted?)")
+                        raise _stalled()
                     continue
                 run = min(min(s.max_new_tokens - len(s.out_tokens)
                               for s in batch), self.MAX_RUN)
@@ -919,9 +649,7 @@ class Engine:
                 remaining = self.step()
                 if remaining and not self.running and \
                         len(self.pending) == n_pending:
-                    raise MemoryError(
-                        "decode stalled: pending prompts cannot be "
-                        "admitted (KV pages exhausted?)")
+                    raise _stalled()
         if torch.cuda.is_available():
             torch.cuda.synchronize()
         self.stats.wall_s += time.perf_counter() - t0
@@ -936,6 +664,11 @@ class Engine:
                 for p, m, sp in zip(prompts, max_new_tokens, per)]
         self.run_to_completion()
         return [s.out_tokens for s in seqs]
+
+
+def _stalled() -> MemoryError:
+    return MemoryError("decode stalled: pending prompts cannot be "
+                       "admitted (KV pages exhausted?)")
 
 
 def _per_prompt(sampling, n: int) -> list:

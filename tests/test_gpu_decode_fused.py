@@ -199,7 +199,7 @@ def test_fused_forced_rescale(ext, D, path):
 
 @pytest.mark.parametrize("D", [64, 128])
 def test_fused_graph_replay_matches_eager_oracle(ext, D):
-    """Captured as Engine._capture_graph captures a decode step
+    """Captured as DecodeGraphs.capture captures DecodeGraphs.step
     (seq_lens += active inside the graph); three replays equal three eager
     steps of the three-kernel path, outputs and caches."""
     QH, KVH, B = 8, 2, 256

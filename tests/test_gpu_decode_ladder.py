@@ -1,11 +1,14 @@
 """Decode-graph ladder on the GPU: the fused greedy sampler kernel against
 the torch ops it replaces, the fp8 skinny GEMM at up to 64 rows and its
-row-invariance across m-tile counts, and the engine's ladder of decode
-graphs against the eager engine."""
+row-invariance across m-tile counts, the engine's ladder of decode graphs
+against the eager engine, and a captured replay of DecodeGraphs.step against
+eager calls of it."""
 
 import pytest
 import torch
 
+from test_decode_graph import (LONG_SCRIPT, PROMPTS, RUN, SHORT_SCRIPT,
+                               _admit, _graphs)
 from test_decode_ladder import (MAX_RUN, SAMPLER_CASES, sampler_case,
                                 torch_sequence)
 
@@ -128,6 +131,12 @@ def _prompts(n):
     return prompts, new
 
 
+def _captured(eng):
+    """The greedy ladder was captured, every rung of it."""
+    return eng.graphs is not None and \
+        set(eng.graphs.greedy) == set(eng.graphs.rungs)
+
+
 def _engine(model, graph):
     from quickstart_streaming_agents_amd.models.serve import Engine
     eng = Engine(model, max_batch=48, max_seq_len=128, eos_id=2,
@@ -150,8 +159,8 @@ def test_engine_ladder_matches_eager(tiny_model, eager_tokens, monkeypatch):
     assert min(new) == 2 and max(new) == 24
     eng = _engine(tiny_model, graph=True)
     out = eng.generate_batch(prompts, new)
-    assert eng._graph is not None, "graph capture failed"
-    assert eng._rungs == serve.ladder_rungs(48)
+    assert _captured(eng), "graph capture failed"
+    assert eng.graphs.rungs == serve.ladder_rungs(48)
     assert out == eager_tokens
     by_rung = eng.stats.decode_steps_by_rung
     assert len(by_rung) >= 2, by_rung
@@ -168,13 +177,13 @@ def test_engine_one_prompt_uses_smallest_rung(tiny_model, monkeypatch):
     i = max(range(20), key=lambda r: new[r])
     eng = _engine(tiny_model, graph=True)
     out = eng.generate_batch([prompts[i]], [new[i]])
-    assert eng._graph is not None, "graph capture failed"
+    assert _captured(eng), "graph capture failed"
     # eager on the same single prompt (the prefill GEMMs are rocBLAS, whose
     # row bits may depend on the other rows of the batch)
     want = _engine(tiny_model, graph=False).generate_batch([prompts[i]],
                                                            [new[i]])
     assert out == want
-    assert set(eng.stats.decode_steps_by_rung) == {eng._rungs[0]}
+    assert set(eng.stats.decode_steps_by_rung) == {eng.graphs.rungs[0]}
     assert set(eng.stats.decode_steps_by_live) == {1}
 
 
@@ -191,7 +200,42 @@ def test_engine_single_graph_switch(tiny_model, eager_tokens, monkeypatch):
     prompts, new = _prompts(20)
     eng = _engine(tiny_model, graph=True)
     out = eng.generate_batch(prompts, new)
-    assert eng._graph is not None, "graph capture failed"
-    assert eng._rungs == (48,)
+    assert _captured(eng), "graph capture failed"
+    assert eng.graphs.rungs == (48,)
     assert out == eager_tokens
     assert set(eng.stats.decode_steps_by_rung) == {48}
+
+
+def test_captured_replay_matches_eager_steps_and_eager_engine(tiny_model,
+                                                              monkeypatch):
+    """One batch (three live rows on rung 16: no script, a script shorter
+    than the run, one longer) from identical engines: graphs.run, fill +
+    eager step calls + read, and the eager engine emit the same tokens."""
+    from quickstart_streaming_agents_amd.models import serve
+    monkeypatch.setattr(serve, "DECODE_LADDER", True)
+    scripts = {1: SHORT_SCRIPT, 2: LONG_SCRIPT}
+    engs = [serve.Engine(tiny_model, max_batch=20, max_seq_len=256, eos_id=2,
+                         valid_vocab=(16, 1000)) for _ in range(3)]
+    batches = [_admit(e, PROMPTS, scripts=scripts) for e in engs]
+    first = [s.out_tokens for s in batches[0]]
+    assert all([s.out_tokens for s in b] == first for b in batches)
+    (e_cap, e_step, e_eager), (b_cap, b_step, b_eager) = engs, batches
+
+    assert e_cap._ensure_graphs(), "graph capture failed"
+    assert e_cap.graphs.rungs == (16, 20)
+    captured, rung, _ = e_cap.graphs.run(b_cap, RUN, False)
+    assert rung == 16
+
+    g = _graphs(e_step)
+    g.fill(b_step, RUN, False)
+    for _ in range(RUN):
+        g.step(16, False)
+    stepped = g.read(len(b_step), RUN)
+    assert captured == stepped
+
+    e_eager._decode_run_eager(b_eager, RUN)
+    want = [s.out_tokens[1:] for s in b_eager]
+    # the eager engine stops a row at EOS; a run's later tokens are dropped
+    assert [t[:len(w)] for t, w in zip(captured, want)] == want
+    assert all(len(w) == RUN or w[-1] == 2 for w in want)
+    assert want[1][:3] == SHORT_SCRIPT and want[2] == LONG_SCRIPT[:RUN]

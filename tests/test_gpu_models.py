@@ -384,7 +384,8 @@ def test_rccl_all_reduce_inside_hipgraph():
         eng_g = Engine(model, max_batch=2, max_seq_len=256)
         assert eng_g.use_graph
         out_g = eng_g.generate_batch([list(p) for p in prompts], [8, 8])
-        assert eng_g._graph is not None, \
+        assert eng_g.graphs is not None and \
+            set(eng_g.graphs.greedy) == set(eng_g.graphs.rungs), \
             "graph capture must succeed with RCCL in the captured region"
 
         eng_e = Engine(model, max_batch=2, max_seq_len=256)
@@ -485,7 +486,8 @@ def test_full_size_llama3_8b_engine():
     prompts = [[1] + list(range(100, 160)), [1] + list(range(300, 340))]
     eng_g = Engine(model, max_batch=2, max_seq_len=512)
     out_g = eng_g.generate_batch([list(p) for p in prompts], [12, 12])
-    assert eng_g._graph is not None
+    assert eng_g.graphs is not None and \
+        set(eng_g.graphs.greedy) == set(eng_g.graphs.rungs)
     eng_e = Engine(model, max_batch=2, max_seq_len=512)
     eng_e.use_graph = False
     out_e = eng_e.generate_batch([list(p) for p in prompts], [12, 12])

@@ -122,6 +122,12 @@ def tiny_model():
     return LlamaModel(LlamaConfig.preset("tiny"), device=DEV)
 
 
+def _captured(eng):
+    """The greedy ladder was captured, every rung of it."""
+    return eng.graphs is not None and \
+        set(eng.graphs.greedy) == set(eng.graphs.rungs)
+
+
 def _engine(model, graph):
     from quickstart_streaming_agents_amd.models.serve import Engine
     eng = Engine(model, max_batch=48, max_seq_len=128, eos_id=2,
@@ -150,10 +156,10 @@ def test_engine_sampled_ladder_matches_eager(tiny_model, monkeypatch):
         prompts, new, sampling=sampling)
     eng = _engine(tiny_model, graph=True)
     out = eng.generate_batch(prompts, new, sampling=sampling)
-    assert eng._graph is not None, "graph capture failed"
-    assert eng._graphs_sampled and not eng._sampled_failed, \
+    assert _captured(eng), "graph capture failed"
+    assert eng.graphs.sampled and not eng.graphs.sampled_failed, \
         "capture of the sampled ladder failed"
-    assert set(eng._graphs_sampled) == set(eng._rungs)
+    assert set(eng.graphs.sampled) == set(eng.graphs.rungs)
     assert out == eager
     by = eng.stats.decode_steps_by_sampler
     assert by["sampled"] > 0
@@ -173,12 +179,12 @@ def test_engine_all_greedy_never_captures_the_second_ladder(tiny_model,
     sampling = [serve.SamplingParams() if i % 3 == 0 else None
                 for i in range(20)]
     out = eng.generate_batch(prompts, new, sampling=sampling)
-    assert eng._graph is not None, "graph capture failed"
+    assert _captured(eng), "graph capture failed"
     assert out == _engine(tiny_model, graph=False).generate_batch(prompts,
                                                                   new)
     assert eng.stats.decode_steps_by_sampler == {
         "greedy": eng.stats.decode_steps, "sampled": 0}
-    assert eng._graphs_sampled == {}
+    assert eng.graphs.sampled == {}
 
 
 # ---- ISA -------------------------------------------------------------------

@@ -99,9 +99,10 @@ def main():
         eng.use_graph = False
     live = args.live or args.batch
     assert 1 <= live <= args.batch
-    if args.rung and eng.use_graph and eng._ensure_graph():
-        eng._rungs = tuple(r for r in eng._rungs if r >= args.rung)
-        assert eng._rungs and eng._rungs[0] >= live, \
+    if args.rung and eng._ensure_graphs():
+        g = eng.graphs
+        g.rungs = tuple(r for r in g.rungs if r >= args.rung)
+        assert g.rungs and g.rungs[0] >= live, \
             f"--rung {args.rung}: no captured rung holds {live} rows"
     runs = measure(eng, args.ctx, live, args.steps, args.warmup, args.repeat)
     ms = statistics.median(runs)

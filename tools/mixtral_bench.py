@@ -27,4 +27,4 @@ for _ in range(args.repeats):
     assert all(len(o) == NEW for o in outs)
     print(f"mixtral-8x7b 1xMI355X: batch {B}, ctx {CTX}, {NEW} new: "
           f"{B*NEW/dt:.0f} decode tok/s incl prefill, wall {dt:.2f}s, "
-          f"graph={'on' if eng._graph is not None else 'off'}", flush=True)
+          f"graph={'on' if eng.graphs is not None else 'off'}", flush=True)

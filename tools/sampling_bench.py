@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-request sampler (ops/hip/sampling.hip) against the torch op sequence
-it stands beside: Engine._sample at temperature > 0 (f32 copy + vocab bias,
-torch.rand, two logs, argmax) on the same bf16 logits.  B = 192 rows of
+it stands beside: TokenPolicy.sample at temperature > 0 (f32 copy + vocab
+bias, torch.rand, two logs, argmax) on the same bf16 logits.  B = 192 rows of
 V = 128256 (randn * 3), window (16, 3335) + eos and the whole vocabulary,
 T = 1, (top_k, top_p) in {(0, 1), (50, 0.9)}.  Results:
 profiles/sampling.md.
@@ -31,7 +31,7 @@ FILTERS = {"plain": (0, 1.0), "k50_p0.9": (50, 0.9)}
 
 
 def torch_sample(logits, bias, temperature=1.0):
-    """Engine._sample at temperature > 0, verbatim."""
+    """TokenPolicy.sample at temperature > 0, verbatim."""
     lg = logits.float() + bias
     u = torch.rand(lg.shape, device=lg.device,
                    dtype=torch.float32).clamp_min_(1e-20)
